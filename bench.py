@@ -162,6 +162,51 @@ def spot_check(sess, tm, first_trace, npix, H=None, n=48):
     return err
 
 
+DUMP_BYTES_MAX = 64 << 20
+DUMP_PIXELS = 256   # per-pixel outputs of the sample; the whole arrays are GBs at the bench's size
+
+
+def dump_outputs(out_dir, gs, sess, npix, means, roi):
+    """--dump-outputs: what the last timed step left for the caller of thz_group_session_recompute, as float32 .npy
+    files under out_dir — the intensity image of the whole grid, the pixel-mean spectra and the region's means as
+    they are, and a fixed seeded sample of rank 0's per-pixel spectra / amplitudes / phases / traces (the sample's
+    pixel indices in sample_pixels.npy).  Read on rank 0 after the timed steps, before anything else reuses the
+    output buffers; at most DUMP_BYTES_MAX in all."""
+    import thz_image_explorer_amd as pkg
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    gx, gy = gs.grid()
+    img = gs.download(pkg.BUF_IMG)
+    if img.nbytes <= DUMP_BYTES_MAX // 2:
+        out["img"] = img.reshape(gx, gy)
+    else:   # grids beyond 4096 x 2048: a seeded sample of the image too (4-byte value + 8-byte index per pixel)
+        at = np.sort(np.random.default_rng(0x1A9E).choice(img.size, size=DUMP_BYTES_MAX // 2 // 12, replace=False))
+        out["img_sample"], out["img_sample_pixels"] = img[at], at.astype(np.float64)
+    if means:
+        out["avg_fft"] = gs.download(pkg.BUF_AVG_FFT)
+        out["avg_amplitudes"] = gs.download(pkg.BUF_AVG_AMPLITUDES)
+        out["avg_phases"] = gs.download(pkg.BUF_AVG_PHASES)
+    if roi:
+        r = gs.roi(0)
+        out.update({f"roi0_{k}": v for k, v in r.items() if k != "count"})
+        out["roi0_count"] = np.array([r["count"]], np.float64)
+    nto = sess.nt_out
+    nf = nto // 2 + 1
+    per_pixel = 4 * (2 * nf + nf + nf + nto)
+    room = DUMP_BYTES_MAX - sum(a.nbytes for a in out.values())
+    n = max(0, min(npix, DUMP_PIXELS, room // (per_pixel + 8)))
+    if n:
+        pix = np.sort(np.random.default_rng(0x5A3D).choice(npix, size=n, replace=False))
+        for name, b in (("fft", pkg.BUF_FFT), ("amplitudes", pkg.BUF_AMPLITUDES), ("phases", pkg.BUF_PHASES), ("data", pkg.BUF_DATA)):
+            out[f"sample_{name}"] = np.concatenate([sess.download(b, int(p), 1) for p in pix])
+        out["sample_pixels"] = pix.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES_MAX
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def wiener_multiplier(eng, tm):
     """K13 of BASELINE config 5 from the synthetic reference pulse (the noise-free template of the cube's traces,
     SURVEY §8d): R through the engine's own window + transform, H by thz_host_wiener_filter"""
@@ -197,7 +242,12 @@ def main():
     ap.add_argument("--no-means", action="store_true", help="no pixel means: the fused launch alone")
     ap.add_argument("--no-roi", action="store_true", help="without the region of interest (the fixed pentagon of SURVEY 8d)")
     ap.add_argument("--no-spot-check", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, a seeded sample of the "
+                         "per-pixel arrays; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -273,6 +323,9 @@ def main():
     roi_ns, roi_calls = eng.timing_collect(binding.STAGE_ROI)
     eng.timing_collect(binding.STAGE_FFT)
     eng.enable_timing(0)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, gs, sess, npix, means=not args.no_means, roi=roi_poly is not None)
     # the run's own correctness witness, before the extra kernel legs below reuse the output buffers
     spot = roi_out = None
     if rank == 0 and not args.no_spot_check:
@@ -389,6 +442,8 @@ def main():
                                   "16 GiB): compare `fused_chain_without_sums` with earlier rounds' roofline.frac, and `config."
                                   "achieved_hbm_pct_whole_step` for the step as a whole") if fused_sums else None},
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nt, ny, args.cpu_seconds)
         print(json.dumps(out), flush=True)

@@ -18,6 +18,10 @@ Fixtures
                        reference's sample_data/example_beam_width (data only)
   roi_masks.npz        integer ROI masks for 8 polygons computed with exact
                        Python ints under the release-mode wrapping rule
+  data_thread_patch_preimage.json
+                       SHA-256 digests of the lines of the reference's
+                       src/data_thread.rs that every hunk of rust/data_thread.patch
+                       replaces, and the file's line count (digests only)
 """
 import os
 import subprocess
@@ -261,6 +265,24 @@ def gen_roi_masks():
     np.savez_compressed(os.path.join(OUT, "roi_masks.npz"), **out)
 
 
+def gen_data_thread_preimage():
+    """tests/golden/data_thread_patch_preimage.json: for every hunk of rust/data_thread.patch, the SHA-256 of the
+    reference's src/data_thread.rs lines in the hunk's old range (bytes as in the file, line ends included), so
+    that tests/test_abi_exports.py checks without the reference that the patch applies there exactly"""
+    import hashlib
+    import json
+    import re
+    lines = open(os.path.join(REF, "src", "data_thread.rs"), "rb").read().splitlines(keepends=True)
+    hunks = []
+    for h in re.finditer(rb"^@@ -(\d+)(?:,(\d+))? \+", open(os.path.join(ROOT, "rust", "data_thread.patch"), "rb").read(), re.M):
+        start, n = int(h[1]), int(h[2] or 1)
+        hunks.append({"old_start": start, "old_len": n,
+                      "sha256": hashlib.sha256(b"".join(lines[start - 1:start - 1 + n])).hexdigest()})
+    with open(os.path.join(OUT, "data_thread_patch_preimage.json"), "w") as f:
+        json.dump({"file": "src/data_thread.rs", "lines": len(lines), "hunks": hunks}, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     gen_fft_vectors()
@@ -269,5 +291,6 @@ if __name__ == "__main__":
     if os.path.isdir(REF):
         gen_knife_edge()
         gen_knife_edge_thz()
+        gen_data_thread_preimage()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -123,16 +123,56 @@ def test_rust_binding_calls_only_what_exists():
         assert "band_pass_fd_ui" not in text and "band_pass_td_ui" not in text, name
 
 
+def _patch_hunks(patch):
+    """[old_start, old_len, pre-image lines] of every hunk of a one-file unified diff (bytes, line ends kept)"""
+    hunks, old, new, last_old = [], 0, 0, False
+    for line in patch.splitlines(keepends=True):
+        m = re.match(rb"@@ -(\d+)(?:,(\d+))? \+\d+(?:,(\d+))? @@", line)
+        if m:
+            old, new = int(m[2] or 1), int(m[3] or 1)
+            hunks.append([int(m[1]), old, []])
+        elif line.startswith(b"\\"):                            # "\ No newline at end of file" of the line before
+            if last_old:
+                hunks[-1][2][-1] = hunks[-1][2][-1].rstrip(b"\r\n")
+        elif old or new:                                        # the header's counts say where the hunk ends
+            last_old = line[:1] != b"+"
+            if last_old:                                        # context (an empty one may lose its blank) / removed
+                hunks[-1][2].append(line[1:] if line[:1] in (b" ", b"-") else line)
+                old -= 1
+            new -= line[:1] != b"-"
+    return hunks
+
+
 def test_data_thread_patch_applies_to_the_reference():
-    ref = "/root/reference/src/data_thread.rs"
-    if not os.path.exists(ref):
-        pytest.skip("the reference is not on this machine")
-    import shutil
+    """rust/data_thread.patch applies to the reference's src/data_thread.rs exactly: no offset, no fuzz.  The
+    reference itself is not part of the repository; tests/golden/data_thread_patch_preimage.json holds the SHA-256
+    of the file's lines in every hunk's old range (scripts/make_golden.py), and every hunk's context and removed
+    lines must hash to them.  `patch --dry-run` then takes the diff against a stand-in file that has those lines
+    at the same places."""
+    import hashlib
+    import json
     import subprocess
     import tempfile
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "data_thread_patch_preimage.json")))
+    patch = open(os.path.join(RUST, "data_thread.patch"), "rb").read()
+    assert patch.startswith(b"--- a/" + golden["file"].encode() + b"\n+++ b/" + golden["file"].encode() + b"\n")
+    hunks = _patch_hunks(patch)
+    assert [(h[0], h[1]) for h in hunks] == [(h["old_start"], h["old_len"]) for h in golden["hunks"]], \
+        "the patch's hunks moved: regenerate the fixture with scripts/make_golden.py next to the reference"
+    end = 0
+    for (start, n, pre), g in zip(hunks, golden["hunks"]):
+        assert len(pre) == n, f"hunk at {start}: {len(pre)} old lines, header says {n}"
+        assert start > end and start - 1 + n <= golden["lines"], f"hunk at {start} overlaps or runs past the file"
+        assert hashlib.sha256(b"".join(pre)).hexdigest() == g["sha256"], f"hunk at {start}: old lines differ from the reference's"
+        end = start - 1 + n
+    stand_in = []
+    for start, n, pre in hunks:
+        stand_in += [b"// line %d\n" % i for i in range(len(stand_in) + 1, start)] + pre
+    stand_in += [b"// line %d\n" % i for i in range(len(stand_in) + 1, golden["lines"] + 1)]
     with tempfile.TemporaryDirectory() as d:
-        os.makedirs(os.path.join(d, "src"))
-        shutil.copy(ref, os.path.join(d, "src", "data_thread.rs"))
+        os.makedirs(os.path.join(d, os.path.dirname(golden["file"])))
+        with open(os.path.join(d, golden["file"]), "wb") as f:
+            f.write(b"".join(stand_in))
         r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(RUST, "data_thread.patch")], cwd=d,
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout
+        assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout and "offset" not in r.stdout, r.stdout

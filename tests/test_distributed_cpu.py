@@ -62,7 +62,9 @@ def _worker(rank, world, port, nx, ny, nt, q):
 
 @pytest.mark.parametrize("nx", [6, 5])  # even split and a ragged one
 def test_two_rank_slab_sharding_matches_single_process(nx):
-    import torch.multiprocessing as mp
+    # torch only in the spawned ranks: imported here it would load its own librccl into the test process, and the
+    # GPU tests' dlopen of librccl.so.1 in the same process would then get that copy instead of the system's
+    import multiprocessing as mp
 
     import oracle_binding as ob
     import synth
@@ -153,7 +155,7 @@ def _voxel_values(seed, n, tiny):
 @pytest.mark.parametrize("n,k,tiny", [(50_001, 2_000, False), (50_001, 30_000, False), (20_000, 500, True),
                                       (1_000, 5_000, False)])
 def test_two_rank_voxel_threshold(n, k, tiny):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp   # torch only in the spawned ranks (see above)
 
     world, seed = 2, 11
     ctx = mp.get_context("spawn")
