@@ -383,9 +383,26 @@ def test_rl_step_kernels(emu, case):
         assert np.abs(res[1][1] - ru).max() / np.abs(ru).max() < 1e-5
 
 
-@pytest.mark.parametrize("case", [dict(h=11, w=13, pr=19, pc=21), dict(h=20, w=37, pr=47, pc=57),
-                                  dict(h=9, w=40, pr=17, pc=33), dict(h=40, w=9, pr=53, pc=5),
-                                  dict(h=6, w=70, pr=3, pc=121)])   # halo wider than two column passes of a wave
+_SEP_CASES = [dict(h=11, w=13, pr=19, pc=21), dict(h=20, w=37, pr=47, pc=57),
+              dict(h=9, w=40, pr=17, pc=33), dict(h=40, w=9, pr=53, pc=5),
+              dict(h=6, w=70, pr=3, pc=121)]   # halo wider than two column passes of a wave
+_SEP_NARROW_CASES = [dict(h=14, w=19, pr=7, pc=9), dict(h=9, w=41, pr=13, pc=17), dict(h=35, w=12, pr=3, pc=5),
+                     dict(h=33, w=34, pr=15, pc=17)]
+
+
+def _separable_inputs(h, w, pr, pc):
+    """padded images d, u and off-centre profiles fx, fy (the mirror differs) with their outer product"""
+    rng = np.random.default_rng(pr * 1000 + pc)
+    H, W = h + 2 * (pr // 2), w + 2 * (pc // 2)
+    d = (0.5 + rng.random((H, W))).astype(np.float32)
+    u = (0.5 + rng.random((H, W))).astype(np.float32)
+    x, y = np.arange(pr) - pr // 2, np.arange(pc) - pc // 2
+    fx = np.exp(-(x - 0.7) ** 2 / (2 * (pr / 5) ** 2)).astype(np.float32)
+    fy = np.exp(-(y + 1.3) ** 2 / (2 * (pc / 6) ** 2)).astype(np.float32)
+    return d, u, fx, fy, np.outer(fx, fy).astype(np.float32)
+
+
+@pytest.mark.parametrize("case", _SEP_CASES)
 def test_rl_step_separable_kernel(emu, case):
     """k_rl_step_sep: a wide kernel that is an outer product fx x fy (every band PSF of the reference is one)
     as a pass along the rows and a pass down the columns — against the reference's loops over the 2-D array and
@@ -393,14 +410,8 @@ def test_rl_step_separable_kernel(emu, case):
     a profile that fills its last chunk exactly (pc = 33 -> 48 staged taps) and one shorter than a chunk"""
     h, w, pr, pc = (case[k] for k in ("h", "w", "pr", "pc"))
     assert pr * pc > 256
-    rng = np.random.default_rng(pr * 1000 + pc)
-    H, W = h + 2 * (pr // 2), w + 2 * (pc // 2)
-    d = (0.5 + rng.random((H, W))).astype(np.float32)
-    u = (0.5 + rng.random((H, W))).astype(np.float32)
-    x, y = np.arange(pr) - pr // 2, np.arange(pc) - pc // 2
-    fx = np.exp(-(x - 0.7) ** 2 / (2 * (pr / 5) ** 2)).astype(np.float32)   # off-centre: the mirror differs
-    fy = np.exp(-(y + 1.3) ** 2 / (2 * (pc / 6) ** 2)).astype(np.float32)
-    psf = np.outer(fx, fy).astype(np.float32)
+    d, u, fx, fy, psf = _separable_inputs(h, w, pr, pc)
+    H, W = d.shape
     res = {}
     for tiled in (0, 1, 2):
         t, un = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
@@ -419,8 +430,7 @@ def test_rl_step_separable_kernel(emu, case):
     assert es <= 2 * e2 + 1e-7 * np.abs(u64).max()
 
 
-@pytest.mark.parametrize("case", [dict(h=14, w=19, pr=7, pc=9), dict(h=9, w=41, pr=13, pc=17), dict(h=35, w=12, pr=3, pc=5),
-                                  dict(h=33, w=34, pr=15, pc=17)])
+@pytest.mark.parametrize("case", _SEP_NARROW_CASES)
 def test_rl_step_separable_kernel_narrow_mode(emu, case):
     """k_rl_step_sep in mode 0: a kernel of <= 256 taps — in the reference a direct sum, correlation-indexed
     (deconvolution.rs:432-458) — that is an outer product, as the same two 1-D passes with the profiles the other way
@@ -428,14 +438,8 @@ def test_rl_step_separable_kernel_narrow_mode(emu, case):
     off-centre profiles so that a wrong direction in either step or either axis would show"""
     h, w, pr, pc = (case[k] for k in ("h", "w", "pr", "pc"))
     assert pr * pc <= 256 and pr % 2 == 1 and pc % 2 == 1
-    rng = np.random.default_rng(pr * 1000 + pc)
-    H, W = h + 2 * (pr // 2), w + 2 * (pc // 2)
-    d = (0.5 + rng.random((H, W))).astype(np.float32)
-    u = (0.5 + rng.random((H, W))).astype(np.float32)
-    x, y = np.arange(pr) - pr // 2, np.arange(pc) - pc // 2
-    fx = np.exp(-(x - 0.7) ** 2 / (2 * (pr / 5) ** 2)).astype(np.float32)
-    fy = np.exp(-(y + 1.3) ** 2 / (2 * (pc / 6) ** 2)).astype(np.float32)
-    psf = np.outer(fx, fy).astype(np.float32)
+    d, u, fx, fy, psf = _separable_inputs(h, w, pr, pc)
+    H, W = d.shape
     res = {}
     for tiled in (1, 2):   # 1: k_rl_step_tiled<false> (reference order), 2: k_rl_step_sep
         t, un = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
@@ -445,6 +449,76 @@ def test_rl_step_separable_kernel_narrow_mode(emu, case):
     assert np.array_equal(res[1][0], rt) and np.array_equal(res[1][1], ru)
     assert np.abs(res[2][0] - rt).max() / np.abs(rt).max() < 2e-6
     assert np.abs(res[2][1] - ru).max() / np.abs(ru).max() < 4e-6
+
+
+# one Richardson-Lucy iteration of k_rl_step_sep per case, in a process of its own: THZ_RL_SEP_THREADS is read once
+# per process.  argv: emulation library, inputs (.npz), outputs (.npz)
+_SEP_CHILD = r"""
+import ctypes as C, sys
+import numpy as np
+lib = C.CDLL(sys.argv[1])
+z = np.load(sys.argv[2])
+p = lambda a: a.ctypes.data_as(C.c_void_p)
+out = {}
+for i in range(int(z["n"])):
+    h, w, pr, pc, mode = (int(v) for v in z["dims%d" % i])
+    psf, fx, fy, d, u = (np.ascontiguousarray(z[k + str(i)]) for k in ("psf", "fx", "fy", "d", "u"))
+    t, un = np.empty_like(d), np.empty_like(d)
+    rc = lib.emu_rl_iteration_sep(h, w, pr, pc, mode, p(psf), p(fx), p(fy), p(d), p(u), 2, p(t), p(un))
+    if rc != 0:
+        sys.exit("case %d: emu_rl_iteration_sep returned %d" % (i, rc))
+    out["t%d" % i], out["u%d" % i] = t, un
+np.savez(sys.argv[3], **out)
+"""
+
+
+def test_rl_step_separable_block_sizes(emu, tmp_path):
+    """k_rl_step_sep<256> and <512> (THZ_RL_SEP_THREADS; by default a launch of more than 512 tiles) stage the halo with
+    fewer rows per batch and deal pass A's tasks over fewer threads, but every pixel's sums run the same tap loop: on the
+    wide and the narrow-mode cases above they must return <1024>'s bits, and <1024> those of the in-process default
+    (these grids are small enough for it), within the same bars against the float64 sums and the reference's loops"""
+    import sys
+    cases = [dict(c, mode=1) for c in _SEP_CASES] + [dict(c, mode=0) for c in _SEP_NARROW_CASES]
+    inputs = {"n": len(cases)}
+    default = []
+    for i, c in enumerate(cases):
+        d, u, fx, fy, psf = _separable_inputs(c["h"], c["w"], c["pr"], c["pc"])
+        inputs.update({"dims%d" % i: [c[k] for k in ("h", "w", "pr", "pc", "mode")],
+                       "psf%d" % i: psf, "fx%d" % i: fx, "fy%d" % i: fy, "d%d" % i: d, "u%d" % i: u})
+        t, un = np.empty_like(d), np.empty_like(d)
+        assert emu.emu_rl_iteration_sep(c["h"], c["w"], c["pr"], c["pc"], c["mode"], _p(psf), _p(fx), _p(fy), _p(d), _p(u),
+                                        2, _p(t), _p(un)) == 0
+        default.append((t, un))
+    np.savez(tmp_path / "in.npz", **inputs)
+    res = {}
+    for threads in (256, 512, 1024):   # one child at a time; the first that fails ends the test
+        out = tmp_path / ("out%d.npz" % threads)
+        env = dict(os.environ, THZ_RL_SEP_THREADS=str(threads))
+        try:
+            r = subprocess.run([sys.executable, "-c", _SEP_CHILD, EMU_SO, str(tmp_path / "in.npz"), str(out)], env=env,
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        except subprocess.TimeoutExpired as e:
+            pytest.fail("THZ_RL_SEP_THREADS=%d: child timed out\n%s" % (threads, e.stderr))
+        if r.returncode != 0:
+            pytest.fail("THZ_RL_SEP_THREADS=%d: child exited %d\n%s" % (threads, r.returncode, r.stderr))
+        z = np.load(out)
+        res[threads] = [(z["t%d" % i], z["u%d" % i]) for i in range(len(cases))]
+    for i, c in enumerate(cases):
+        for threads in (256, 512):
+            assert np.array_equal(res[threads][i][0], res[1024][i][0]), (c, threads)
+            assert np.array_equal(res[threads][i][1], res[1024][i][1]), (c, threads)
+        assert np.array_equal(res[1024][i][0], default[i][0]) and np.array_equal(res[1024][i][1], default[i][1]), c
+        d, u = inputs["d%d" % i], inputs["u%d" % i]
+        psf = inputs["psf%d" % i]
+        if c["mode"] == 1:
+            rt = d / (_conv_same_f64(u, psf) + 1e-12)
+            ru = u * _conv_same_f64(rt, psf[::-1, ::-1])
+        else:
+            rt, ru = _rl_reference(d, u, psf, 0)
+        for threads in (256, 512, 1024):
+            t, un = res[threads][i]
+            assert np.abs(t - rt).max() / np.abs(rt).max() < 2e-6, (c, threads)
+            assert np.abs(un - ru).max() / np.abs(ru).max() < 4e-6, (c, threads)
 
 
 def _conv_same_f64(a, k):
