@@ -976,3 +976,183 @@ def test_mixed_radix_stage_kernels_two_pairs_per_wave(emu, nt):
             assert np.abs(res[1][3]).max() > 0
     finally:
         emu.emu_set_p_pairs(0)
+
+
+# ------------------------------------------------------------------ every trace to its own scale (trace_isolation.py)
+# The P and chirp-z kernels pack two real traces into one complex transform.  These tests hold each trace to 1e-5 of
+# its OWN float64 spectrum / trace across partners up to 1e6 apart, zero traces, and non-finite samples; the
+# one-trace-per-wave families (F, PH, global scratch) are the controls.
+import trace_isolation as ti
+
+ISO_CASES = [  # (nt, family code of emu_family, allow_p)
+    (1001, 6, 1), (1000, 6, 1), (1200, 6, 1), (1500, 6, 1), (2000, 6, 1),
+    (640, 2, 1), (777, 2, 1), (1023, 2, 1), (1502, 3, 1), (2047, 3, 1), (3001, 4, 1), (5000, 5, 1), (8191, 5, 1),
+    (1001, 2, 0),                                                       # 1001 forced onto the chirp-z kernels
+    (1024, 1, 1), (4096, 1, 1), (2002, 3, 1), (4000, 4, 1), (10000, 0, 1),  # controls: F, PH, global scratch
+]
+ISO_IDS = [f"{nt}-{'nop' if not ap else fam}" for nt, fam, ap in ISO_CASES]
+
+
+def _iso_setup(emu, nt, fam, allow_p, pairs=1):
+    emu.emu_allow_f(1)
+    emu.emu_allow_p(allow_p)
+    emu.emu_set_p_pairs(pairs)
+    emu.emu_set_grid_cap(1 if nt > 8192 else 0)   # global scratch: one block of four waves, as the long-trace test does
+    assert emu.emu_family(nt) == fam
+    if nt in (2002, 4000):
+        assert emu.emu_half_n(nt) == nt // 2   # PH: one trace per wave
+
+
+def _iso_reset(emu):
+    emu.emu_set_p_pairs(0)
+    emu.emu_set_grid_cap(0)
+    emu.emu_allow_p(1)
+
+
+def _iso_chain(nt):
+    time = synth.make_time(nt)
+    return synth.default_chain(time)
+
+
+def _emu_forward(emu, nt, x, chain, with_data_out):
+    n, nf = x.shape[0], nt // 2 + 1
+    fft = np.zeros((n, nf, 2), np.float32); amp = np.zeros((n, nf), np.float32); ph = np.zeros((n, nf), np.float32)
+    if with_data_out:   # two windows whose product is w_pre, and the windowed-trace output
+        dout = np.zeros_like(x)
+        rc = emu.emu_fft_fwd(nt, C.c_size_t(n), _p(x), _p(chain["w_tilt"] * chain["w_td_before"]), _p(chain["w_fft"]),
+                             _p(dout), _p(fft), _p(amp), _p(ph), _p(chain["fd_mask"]))
+        pre = (chain["w_tilt"] * chain["w_td_before"]).astype(np.float32)
+        xin = (x * pre) * chain["w_fft"]   # what the kernel transforms: the two windows applied in turn, in f32
+        return rc, fft, amp, ph, xin
+    rc = emu.emu_fft_fwd(nt, C.c_size_t(n), _p(x), _p(chain["w_pre"]), None, None, _p(fft), _p(amp), _p(ph),
+                         _p(chain["fd_mask"]))
+    return rc, fft, amp, ph, x * chain["w_pre"]
+
+
+def _emu_chain(emu, nt, x, chain, mode):
+    """the fused chain: mode 'pipeline' (emu_pipeline), 'cmask' (emu_pipeline_ex), 'sums' / 'cmask+sums'
+    (emu_pipeline_sums) -> fft, amp, ph, out, img, H"""
+    n, nf = x.shape[0], nt // 2 + 1
+    fft = np.zeros((n, nf, 2), np.float32); amp = np.zeros((n, nf), np.float32); ph = np.zeros((n, nf), np.float32)
+    out = np.zeros_like(x); img = np.zeros(n, np.float32)
+    H = _wiener_cmask(chain["time"], nf) if "cmask" in mode else None
+    args = (_p(fft), _p(amp), _p(ph), _p(out), _p(img))
+    if mode == "pipeline":
+        rc = emu.emu_pipeline(nt, C.c_size_t(n), _p(x), _p(chain["w_pre"]), _p(chain["fd_mask"]), _p(chain["w_post"]), *args)
+        assert rc == 0
+    elif "sums" in mode:
+        sums = np.zeros(2 * nf, np.float32)
+        rc = emu.emu_pipeline_sums(nt, C.c_size_t(n), _p(x), _p(chain["w_pre"]), _p(chain["fd_mask"]), _p(H),
+                                   _p(chain["w_post"]), *args, _p(sums))
+        assert rc >= 1
+    else:
+        rc = emu.emu_pipeline_ex(nt, C.c_size_t(n), _p(x), _p(chain["w_pre"]), _p(chain["fd_mask"]), _p(H),
+                                 _p(chain["w_post"]), *args)
+        assert rc == 0
+    return fft, amp, ph, out, img, H
+
+
+def _iso_check_chain(nt, x, chain, res, st=None, factors=ti.FACTORS):
+    fft, amp, ph, out, img, H = res
+    st = ti.status(factors) if st is None else st
+    ref = ti.forward_ref(x * chain["w_pre"], None, chain["fd_mask"], H)
+    y, e = ti.inverse_ref(ref["fft"], nt, chain["w_post"])
+    bad = ti.check("fft", ti.as_complex(fft), ref["fft"], st) + ti.check("amp", amp, ref["amp"], st)
+    bad += ti.check("out", out, y, st) + ti.check_intensity(img, e, st) + ti.check_phases(ph, ref, st, factors)
+    for i in ti.CLEAN_NEXT_TO_BAD if factors is ti.FACTORS else ():
+        assert np.isfinite(fft[i]).all() and np.isfinite(out[i]).all() and np.isfinite(ph[i]).all()
+    return bad
+
+
+@pytest.mark.parametrize("nt,fam,allow_p", ISO_CASES, ids=ISO_IDS)
+def test_trace_isolation_forward_inverse(emu, nt, fam, allow_p):
+    """fft (with and without the windowed-trace output and second window) and ifft: every trace within 1e-5 of its
+    own float64 spectrum / trace, zero traces exactly zero, the clean partner of a NaN / Inf trace unharmed"""
+    _iso_setup(emu, nt, fam, allow_p)
+    try:
+        chain = _iso_chain(nt)
+        x = ti.make_cube(nt)
+        st = ti.status()
+        bad = []
+        for with_data_out in (False, True):
+            rc, fft, amp, ph, xin = _emu_forward(emu, nt, x, chain, with_data_out)
+            assert rc == 0
+            ref = ti.forward_ref(xin, None, chain["fd_mask"])
+            tag = "+data_out" if with_data_out else ""
+            bad += [tag + b for b in ti.check("fft", ti.as_complex(fft), ref["fft"], st)
+                    + ti.check("amp", amp, ref["amp"], st) + ti.check_phases(ph, ref, st)]
+            for i in ti.CLEAN_NEXT_TO_BAD:
+                assert np.isfinite(fft[i]).all()
+        # inverse of finite spectra: the float64 spectra rounded to f32, their scales as the cube's
+        ref = ti.forward_ref(x * chain["w_pre"], None, chain["fd_mask"])
+        Yin = np.nan_to_num(ref["fft"], nan=0.0, posinf=0.0, neginf=0.0)
+        fin = np.ascontiguousarray(np.stack([Yin.real, Yin.imag], -1).astype(np.float32))
+        for i in ti.BAD:
+            fin[i, 5, 0] = np.nan if i == ti.BAD[0] else np.inf
+        out = np.zeros_like(x); img = np.zeros(x.shape[0], np.float32)
+        assert emu.emu_fft_inv(nt, C.c_size_t(x.shape[0]), _p(fin), _p(chain["w_post"]), _p(out), _p(img)) == 0
+        y, e = ti.inverse_ref(ti.as_complex(fin), nt, chain["w_post"])
+        bad += ["ifft " + b for b in ti.check("out", out, y, st) + ti.check_intensity(img, e, st)]
+        assert not bad, "; ".join(bad[:12])
+    finally:
+        _iso_reset(emu)
+
+
+
+
+@pytest.mark.parametrize("pairs", [1, 2])
+@pytest.mark.parametrize("nt,fam,allow_p", ISO_CASES, ids=ISO_IDS)
+def test_trace_isolation_fused_chain(emu, nt, fam, allow_p, pairs):
+    """the fused chain (pipeline), and at the P and F lengths pipeline_ex with a complex multiplier and with the
+    in-launch pixel sums; at the P lengths with one and with two pairs of traces per wave"""
+    if pairs == 2 and not (fam == 6 and nt in (1001, 1000)):
+        pytest.skip("two pairs per wave exist for the P kernels of 1001 and 1000 only")
+    _iso_setup(emu, nt, fam, allow_p, pairs)
+    try:
+        chain = _iso_chain(nt)
+        x = ti.make_cube(nt)
+        modes = ["pipeline"]
+        if fam == 6 or (fam == 1 and nt <= 4096):
+            modes += ["cmask"] + (["sums", "cmask+sums"] if pairs == 1 else [])
+        bad = []
+        for mode in modes:
+            bad += [f"{mode} {b}" for b in _iso_check_chain(nt, x, chain, _emu_chain(emu, nt, x, chain, mode))]
+        assert not bad, "; ".join(bad[:12])
+    finally:
+        _iso_reset(emu)
+
+
+@pytest.mark.parametrize("nt,fam,allow_p", [c for c in ISO_CASES if c[1] in (2, 3, 4, 5, 6) and c[0] not in (2002, 4000)],
+                         ids=[i for c, i in zip(ISO_CASES, ISO_IDS) if c[1] in (2, 3, 4, 5, 6) and c[0] not in (2002, 4000)])
+def test_trace_isolation_partner_independence(emu, nt, fam, allow_p):
+    """a trace scaled by 2^k (k = -30, -10, 10) leaves its partner's outputs bit-identical and comes out scaled by
+    2^k itself (to the per-trace bar); fused chain and the stand-alone forward transform"""
+    _iso_setup(emu, nt, fam, allow_p)
+    try:
+        chain = _iso_chain(nt)
+        factors = [1.0, 1e-3, 1e-4, 1.0, 1.0, 1.0, 1e2, 1.0, 1.0]
+        x0 = ti.make_cube(nt, factors)
+        base = _emu_chain(emu, nt, x0, chain, "pipeline")
+        base_f = _emu_forward(emu, nt, x0, chain, False)
+        for moved in (0, 1):    # the first or the second trace of every pair
+            for k in (-30, -10, 10):
+                x = x0.copy()
+                idx = np.arange(moved, x.shape[0], 2)
+                x[idx] *= np.float32(2.0 ** k)
+                res = _emu_chain(emu, nt, x, chain, "pipeline")
+                res_f = _emu_forward(emu, nt, x, chain, False)
+                others = np.setdiff1d(np.arange(x.shape[0]), idx)
+                others = others[(others ^ 1) < x.shape[0]]    # partners only (the odd last trace has none)
+                for a, b in list(zip(res[:5], base[:5])) + list(zip(res_f[1:4], base_f[1:4])):
+                    assert np.array_equal(np.asarray(a)[others].view(np.uint32), np.asarray(b)[others].view(np.uint32)), \
+                        f"moved={moved} k={k}: a partner's outputs changed"
+                s = 2.0 ** k
+                st = ["live" if i in idx else "skip" for i in range(x.shape[0])]
+                bad = ti.check("fft", ti.as_complex(res[0]), ti.as_complex(base[0]) * s, st)
+                bad += ti.check("amp", res[1], base[1].astype(np.float64) * s, st)
+                bad += ti.check("out", res[3], base[3].astype(np.float64) * s, st)
+                bad += ti.check_intensity(res[4], base[4].astype(np.float64) * s * s, st)
+                d = np.abs(res[2][idx].astype(np.float64) - base[2][idx])
+                assert not bad and d.max() < 1e-3, f"moved={moved} k={k}: " + "; ".join(bad[:8]) + f" phase {d.max():.1e}"
+    finally:
+        _iso_reset(emu)

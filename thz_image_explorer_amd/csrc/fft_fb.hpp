@@ -238,19 +238,24 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
         // lane parts of the indices, opaque per trace: otherwise every clamped index, compare mask and
         // address of the unrolled loops below is hoisted out of the trace loop and lives (spills) forever
         const int lb = launder_v(C1 * lane), lb4 = launder_v(4 * lane), lb1 = launder_v(lane);
+        float sc_out1 = 1.0f, sc_out2 = 1.0f;  // the forward PairScale::out of the two traces
+        bool zero1 = false, zero2 = false;
+        unsigned ym1 = 0u, ym2 = 0u;           // largest |component| of the two masked spectra (the inverse's PairScale)
 
         if constexpr (MODE != kInv) {
         // ---- a[n] = (x1[n] + i x2[n]) pre[n] w[n] (zero from nt on), in the core's input layout.
         // Branch-free: indices are clamped and the value selected, so that the loads of a trace are
         // issued together instead of one exec-masked round trip each
+        // The windowed samples go to r first (x1 pre as real, x2 pre as imaginary part) and each trace's largest
+        // |value| is taken (PairScale); the chirp multiply follows once both scales are known.
         {
             const float *x1 = A.in + p * (size_t)L;
             const float *x2 = has2 ? x1 + L : x1;
-            constexpr int H = R1 / 2;  // two batches: 4 registers per element in flight, not for all 32
+            constexpr int H = R1 / 2;  // two batches: 2 registers per element in flight, not for all 32
+            unsigned ma = 0u, mb = 0u;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 float xa[C1][H], xb[C1][H];
-                cx wv[C1][H];
 #pragma unroll
                 for (int j = 0; j < H; ++j) {
 #pragma unroll
@@ -259,7 +264,6 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                         const unsigned nn = (unsigned)(n < L ? n : L - 1);
                         xa[c][j] = ld_off(x1, nn);
                         xb[c][j] = ld_off(x2, nn);
-                        wv[c][j] = ld_off(wl, nn);
                     }
                 }
 #pragma unroll
@@ -270,6 +274,33 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                         const int nn = n < L ? n : L - 1;
                         const float pw = n < L ? pre_l[nn] : 0.0f;
                         const cx z = cx{xa[c][j] * pw, has2 ? xb[c][j] * pw : 0.0f};
+                        ma = umax(ma, abs_bits(z.x));
+                        mb = umax(mb, abs_bits(z.y));
+                        r[c][H * h + j] = z;
+                    }
+                }
+                THZ_SCHED_FENCE();
+            }
+            const PairScale e1(wave_reduce_max_u32(ma)), e2(wave_reduce_max_u32(mb));
+            sc_out1 = e1.out; sc_out2 = e2.out; zero1 = e1.zero; zero2 = e2.zero;
+            const bool any_bad = e1.bad || e2.bad;  // wave-uniform and rare: a non-finite trace enters as zeros
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                cx wv[C1][H];
+#pragma unroll
+                for (int j = 0; j < H; ++j)
+#pragma unroll
+                    for (int c = 0; c < C1; ++c) {
+                        const int n = M1 * (H * h + j) + lb + c;
+                        wv[c][j] = ld_off(wl, (unsigned)(n < L ? n : L - 1));
+                    }
+#pragma unroll
+                for (int j = 0; j < H; ++j) {
+#pragma unroll
+                    for (int c = 0; c < C1; ++c) {
+                        cx z = r[c][H * h + j];
+                        z = cx{z.x * e1.in, z.y * e2.in};
+                        if (any_bad) z = cx{e1.bad ? 0.0f : z.x, e2.bad ? 0.0f : z.y};
                         r[c][H * h + j] = cx_mul(z, wv[c][j]);
                     }
                 }
@@ -285,6 +316,7 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
 
         // ---- spectrum epilogue: F[k] = w[k] c[k]; X1 = (F[k] + conj F[nt-k]) / 2, X2 = (F[k] - conj F[nt-k]) / 2i
         {
+            const float h1 = 0.5f * sc_out1, h2 = 0.5f * sc_out2;
             FBUnwrap u1, u2;
             for (int g = 0; g < n_groups; ++g) {
                 const int k0 = 256 * g + lb4;
@@ -302,15 +334,17 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                     const cx Fk = cx_mul(cx{s.y, s.x}, wk);
                     const cx wm = kc == 0 ? wk : cx{sgn * wk.x, sgn * wk.y};
                     const cx Fm = cx_mul(cx{sm.y, sm.x}, wm);
-                    // conj(Fm) = (Fm.x, -Fm.y)
-                    X1[c] = cx{0.5f * (Fk.x + Fm.x), 0.5f * (Fk.y - Fm.y)};
+                    // conj(Fm) = (Fm.x, -Fm.y); the 1/2 carries each trace's 2^e (PairScale)
+                    X1[c] = cx{h1 * (Fk.x + Fm.x), h1 * (Fk.y - Fm.y)};
                     // (Fk - conj Fm) / 2i = (-i/2) (dx + i dy) = (dy/2, -dx/2)
-                    X2[c] = cx{0.5f * (Fk.y + Fm.y), -0.5f * (Fk.x - Fm.x)};
+                    X2[c] = cx{h2 * (Fk.y + Fm.y), -h2 * (Fk.x - Fm.x)};
                     m[c] = mask_l[kc];
                     if (kc == 0 || ((L & 1) == 0 && kc == nf - 1)) {  // real input: DC / Nyquist bins are real
                         X1[c].y = 0.0f;
                         X2[c].y = 0.0f;
                     }
+                    if (zero1) X1[c] = cx{0.0f, 0.0f};  // wave-uniform: a zero trace's spectrum is +0.0
+                    if (zero2) X2[c] = cx{0.0f, 0.0f};
                 }
                 const size_t o1 = p * (size_t)nf + k0;
                 fb_finish_bins(X1, m, ok, g, lane, u1, A.fft_out ? A.fft_out + o1 : nullptr,
@@ -324,9 +358,13 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
                         if (ok[c]) {
-                            buf[nat(k0 + c)] = cx{X1[c].x * m[c], X1[c].y * m[c]};
+                            const cx y1 = cx{X1[c].x * m[c], X1[c].y * m[c]};
                             // a missing second trace is exactly zero, as in the stand-alone inverse
-                            buf[nat(y2_base + k0 + c)] = has2 ? cx{X2[c].x * m[c], X2[c].y * m[c]} : cx{0.0f, 0.0f};
+                            const cx y2 = has2 ? cx{X2[c].x * m[c], X2[c].y * m[c]} : cx{0.0f, 0.0f};
+                            ym1 = umax(ym1, umax(abs_bits(y1.x), abs_bits(y1.y)));
+                            ym2 = umax(ym2, umax(abs_bits(y2.x), abs_bits(y2.y)));
+                            buf[nat(k0 + c)] = y1;
+                            buf[nat(y2_base + k0 + c)] = y2;
                         }
                 }
             }
@@ -343,12 +381,16 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                     y1.y = 0.0f;
                     y2.y = 0.0f;
                 }
+                ym1 = umax(ym1, umax(abs_bits(y1.x), abs_bits(y1.y)));
+                ym2 = umax(ym2, umax(abs_bits(y2.x), abs_bits(y2.y)));
                 buf[nat(k)] = y1;
                 buf[nat(y2_base + k)] = y2;
             }
             wave_sync();
         }
         if constexpr (MODE == kFwd) continue;
+        // each masked spectrum's PairScale: applied as it is packed, undone on the window post[n]
+        const PairScale e1(wave_reduce_max_u32(ym1)), e2(wave_reduce_max_u32(ym2));
 
         // ---- inverse: a'[n] = conj(Y1full[n] + i Y2full[n]) w[n];  Yfull[n] = Y[n] (n <= nt/2), conj(Y[nt-n]) above
         {
@@ -372,6 +414,8 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                         const bool low = nn <= half;
                         const int kk = low ? nn : L - nn;
                         cx y1 = buf[nat(kk)], y2 = buf[nat(y2_base + kk)];
+                        y1 = e1.bad ? cx{0.0f, 0.0f} : cx{y1.x * e1.in, y1.y * e1.in};
+                        y2 = e2.bad ? cx{0.0f, 0.0f} : cx{y2.x * e2.in, y2.y * e2.in};
                         // Yfull = low ? Y : conj(Y);  G = Y1full + i Y2full;  conj(G) = conj(Y1full) - i conj(Y2full)
                         // low : conj(Y1) - i conj(Y2) = (y1.x - y2.y, -y1.y - y2.x)
                         // high: Y1 - i Y2             = (y1.x + y2.y,  y1.y - y2.x)
@@ -401,11 +445,11 @@ __global__ __launch_bounds__(512) void k_fb(FBArgs A, FTables T)
                 const cx wv = ld_off(wl, (unsigned)n);
                 const cx U = cx_mul(cx{s.y, s.x}, wv);
                 const float pw = post_l[n];
-                const float v1 = by_nt(U.x) * pw;
+                const float v1 = by_nt(U.x) * (pw * e1.out);
                 o1[n] = v1;
                 acc1 += v1 * v1;
                 if (has2) {
-                    const float v2 = by_nt(-U.y) * pw;
+                    const float v2 = by_nt(-U.y) * (pw * e2.out);
                     o1[L + n] = v2;
                     acc2 += v2 * v2;
                 }
@@ -552,6 +596,33 @@ __global__ __launch_bounds__(512) void k_fbc(FB2Args B, FTables T)
         const float *post_g = A.post_win ? launder_uniform(A.post_win) : nullptr;
         const int lb = launder_v(C1 * lane), lb4 = launder_v(4 * lane), lb1 = launder_v(lane);
 
+        // each trace's PairScale, from its largest windowed sample (forward) or spectrum component (inverse): every
+        // wave of the pair reads the whole of both traces anyway, so each takes the maxima itself
+        unsigned ma = 0u, mb = 0u;
+        if (valid) {
+            if constexpr (MODE == kFwd) {
+                const float *x1 = A.in + p * (size_t)L;
+                for (int n = lb1; n < L; n += kWave) {
+                    const float pw = pre_g ? ld_off(pre_g, (unsigned)n) : 1.0f;
+                    ma = umax(ma, abs_bits(ld_off(x1, (unsigned)n) * pw));
+                    if (has2) mb = umax(mb, abs_bits(ld_off(x1, (unsigned)(L + n)) * pw));
+                }
+            } else {
+                const cx *f1 = A.fft_in + p * (size_t)nf;
+                for (int k = lb1; k < nf; k += kWave) {
+                    const bool rb = k == 0 || ((L & 1) == 0 && k == nf - 1);
+                    const cx y1 = ld_off(f1, (unsigned)k);
+                    ma = umax(ma, umax(abs_bits(y1.x), rb ? 0u : abs_bits(y1.y)));
+                    if (has2) {
+                        const cx y2 = ld_off(f1, (unsigned)(nf + k));
+                        mb = umax(mb, umax(abs_bits(y2.x), rb ? 0u : abs_bits(y2.y)));
+                    }
+                }
+            }
+        }
+        const PairScale e1(wave_reduce_max_u32(ma)), e2(wave_reduce_max_u32(mb));
+        const bool any_bad = e1.bad || e2.bad;  // wave-uniform and rare: a non-finite trace enters as zeros
+
         auto f_at = [&](int m) -> cx {
             const int mm = m < L ? m : L - 1;
             cx v;
@@ -560,7 +631,9 @@ __global__ __launch_bounds__(512) void k_fbc(FB2Args B, FTables T)
                 const float pw = pre_g ? ld_off(pre_g, (unsigned)mm) : 1.0f;
                 const float xa = ld_off(x1, (unsigned)mm);
                 const float xb = has2 ? ld_off(x1, (unsigned)(L + mm)) : 0.0f;
-                v = cx_mul(cx{xa * pw, xb * pw}, ld_off(wl, (unsigned)mm));
+                cx z = cx{(xa * pw) * e1.in, (xb * pw) * e2.in};
+                if (any_bad) z = cx{e1.bad ? 0.0f : z.x, e2.bad ? 0.0f : z.y};
+                v = cx_mul(z, ld_off(wl, (unsigned)mm));
             } else {
                 const cx *f1 = A.fft_in + p * (size_t)nf;
                 const bool low = mm <= half;
@@ -571,6 +644,8 @@ __global__ __launch_bounds__(512) void k_fbc(FB2Args B, FTables T)
                     y1.y = 0.0f;
                     y2.y = 0.0f;
                 }
+                y1 = e1.bad ? cx{0.0f, 0.0f} : cx{y1.x * e1.in, y1.y * e1.in};
+                y2 = e2.bad ? cx{0.0f, 0.0f} : cx{y2.x * e2.in, y2.y * e2.in};
                 const cx gc = low ? cx{y1.x - y2.y, -y1.y - y2.x} : cx{y1.x + y2.y, y1.y - y2.x};
                 v = cx_mul(gc, ld_off(wl, (unsigned)mm));
             }
@@ -618,18 +693,21 @@ __global__ __launch_bounds__(512) void k_fbc(FB2Args B, FTables T)
             cx X1[2][4], X2[2][4];
             float mk[2][4], sr1[2][4], sr2[2][4], ex1[2], ex2[2];
             float first1 = 0.0f, first2 = 0.0f;
+            const float h1 = 0.5f * e1.out, h2 = 0.5f * e2.out;  // the split's 1/2 carries each trace's 2^e
             auto spectra_at = [&](int kc, cx &x1v, cx &x2v) {
                 const int km = kc == 0 ? 0 : L - kc;  // F[nt] = F[0]
                 const cx wk = ld_off(wl, (unsigned)kc);
                 const cx Fk = cx_mul(fbs_c<P, S>(reg0, tw, kc), wk);
                 const cx wm = kc == 0 ? wk : cx{sgn * wk.x, sgn * wk.y};
                 const cx Fm = cx_mul(fbs_c<P, S>(reg0, tw, km), wm);
-                x1v = cx{0.5f * (Fk.x + Fm.x), 0.5f * (Fk.y - Fm.y)};
-                x2v = cx{0.5f * (Fk.y + Fm.y), -0.5f * (Fk.x - Fm.x)};
+                x1v = cx{h1 * (Fk.x + Fm.x), h1 * (Fk.y - Fm.y)};
+                x2v = cx{h2 * (Fk.y + Fm.y), -h2 * (Fk.x - Fm.x)};
                 if (kc == 0 || ((L & 1) == 0 && kc == nf - 1)) {
                     x1v.y = 0.0f;
                     x2v.y = 0.0f;
                 }
+                if (e1.zero) x1v = cx{0.0f, 0.0f};  // wave-uniform: a zero trace's spectrum is +0.0
+                if (e2.zero) x2v = cx{0.0f, 0.0f};
             };
             if (valid) {
                 {   // raw phase of bin 0 (every wave needs it; cheaper to evaluate than to pass around)
@@ -743,11 +821,11 @@ __global__ __launch_bounds__(512) void k_fbc(FB2Args B, FTables T)
                 for (int n = s * chunk + lb1; n < n_end; n += kWave) {
                     const cx U = cx_mul(fbs_c<P, S>(reg0, tw, n), ld_off(wl, (unsigned)n));
                     const float pw = post_g ? ld_off(post_g, (unsigned)n) : 1.0f;
-                    const float v1 = by_nt(U.x) * pw;
+                    const float v1 = by_nt(U.x) * (pw * e1.out);
                     o1[n] = v1;
                     acc1 += v1 * v1;
                     if (has2) {
-                        const float v2 = by_nt(-U.y) * pw;
+                        const float v2 = by_nt(-U.y) * (pw * e2.out);
                         o1[L + n] = v2;
                         acc2 += v2 * v2;
                     }

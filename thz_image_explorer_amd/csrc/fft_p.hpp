@@ -310,6 +310,38 @@ __device__ __forceinline__ float p_zero_if(float v, bool zero)
     return __builtin_bit_cast(float, bits);
 }
 
+// input of the inverse for bin k: conj(G[k]) and conj(G[N-k]) of G = Y1full + i Y2full (Yfull[n] = Y[n] up to N/2,
+// conj(Y[N-n]) above), each spectrum times its PairScale first (a non-finite one enters as zeros)
+template <int N>
+__device__ __forceinline__ void p_pack_bin(cx *bq, int k, cx y1, cx y2, const PairScale &e1, const PairScale &e2)
+{
+    y1 = e1.bad ? cx{0.0f, 0.0f} : cx{y1.x * e1.in, y1.y * e1.in};
+    y2 = e2.bad ? cx{0.0f, 0.0f} : cx{y2.x * e2.in, y2.y * e2.in};
+    bq[k] = cx{y1.x - y2.y, -y1.y - y2.x};
+    if (k != 0 && 2 * k != N) bq[N - k] = cx{y1.x + y2.y, y1.y - y2.x};
+}
+
+// the fused chain's packing, once the masked spectra of the pair are in bq unpacked (Y1[k] in slot k, Y2[k] in slot
+// N-k, a real bin's two real values in its one slot) and their scales known; bins as in the epilogue, so every lane
+// reads only the slots it wrote
+template <int N, int NF>
+__device__ __forceinline__ void p_pack_inverse(cx *bq, int lb4, const PairScale &e1, const PairScale &e2)
+{
+    constexpr int n_groups = (NF + 255) / 256;
+#pragma unroll 1
+    for (int g = 0; g < n_groups; ++g) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int k = 256 * g + lb4 + c;
+            if (k < NF) {
+                const bool real_bin = k == 0 || 2 * k == N;
+                const cx a = bq[k], b = real_bin ? cx{0.0f, 0.0f} : bq[N - k];
+                p_pack_bin<N>(bq, k, real_bin ? cx{a.x, 0.0f} : a, real_bin ? cx{a.y, 0.0f} : b, e1, e2);
+            }
+        }
+    }
+}
+
 // In-launch pixel sums of the stored amplitudes and unwrapped phases (the numerators of the ifft stage's pixel means,
 // math_tools.rs:427-440), as in the F kernels (fft_f.hpp, FSums): the block keeps one set of accumulators in LDS and
 // its waves add to it group by group in TICKET order — wave w's visit of group g in its r-th trip has ticket
@@ -432,6 +464,9 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
         const int lb4 = launder_v(4 * lane), lb1 = launder_v(lane);
         // traces of the unit that exist (wave-uniform): n_tr in 1 .. 2 Q
         const int n_tr = (int)((A.npix - p0) < (size_t)(2 * Q) ? (A.npix - p0) : (size_t)(2 * Q));
+        float i_out[Q][2];  // the inverse's PairScale::out of trace 2 q + t of the unit
+#pragma unroll
+        for (int q = 0; q < Q; ++q) i_out[q][0] = i_out[q][1] = 0.0f;
 
         if constexpr (MODE != kInv) {
             // ---- pass 1 from memory: z[n] = (x1[n] + i x2[n]) pre[n], n = M1 j1 + m.  Every round's loads are
@@ -450,17 +485,59 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                     xb[i][j1] = ld_off(x0, gb + (unsigned)(M1 * j1));
                 }
             }
+            // windowed samples, and each trace's largest |value| (PairScale): trace 2 q + t of the unit in mx[q][t]
+            unsigned mx[Q][2];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) mx[q][0] = mx[q][1] = 0u;
+#pragma unroll
+            for (int i = 0; i < RD1; ++i) {
+                const int m = ad.m1[i];
+                const int q2 = 2 * (ad.g1[i] / (2 * N));
+                const float sa = q2 < n_tr ? 1.0f : 0.0f, sb = q2 + 1 < n_tr ? 1.0f : 0.0f;
+                unsigned ma = 0u, mb = 0u;
+#pragma unroll
+                for (int j1 = 0; j1 < R1; ++j1) {
+                    const float pw = pre_l[M1 * j1 + m];
+                    xa[i][j1] *= pw * sa;
+                    xb[i][j1] *= pw * sb;
+                    ma = umax(ma, abs_bits(xa[i][j1]));
+                    mb = umax(mb, abs_bits(xb[i][j1]));
+                }
+#pragma unroll
+                for (int q = 0; q < Q; ++q)
+                    if (Q == 1 || q2 == 2 * q) {
+                        mx[q][0] = umax(mx[q][0], ma);
+                        mx[q][1] = umax(mx[q][1], mb);
+                    }
+            }
+            float s_in[Q][2], s_out[Q][2];
+            bool s_zero[Q][2], any_bad = false;
+            unsigned bad_mask = 0u;  // bit 2 q + t: trace 2 q + t is not finite
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const PairScale sc(wave_reduce_max_u32(mx[q][t]));
+                    s_in[q][t] = sc.in;
+                    s_out[q][t] = sc.out;
+                    s_zero[q][t] = sc.zero;
+                    if (sc.bad) bad_mask |= 1u << (2 * q + t);
+                }
+            any_bad = bad_mask != 0u;
 #pragma unroll
             for (int i = 0; i < RD1; ++i) {
                 const bool on = lane + kWave * i < Q * P::B1;
                 const int m = ad.m1[i];
                 const int q2 = 2 * (ad.g1[i] / (2 * N));
-                const float sa = q2 < n_tr ? 1.0f : 0.0f, sb = q2 + 1 < n_tr ? 1.0f : 0.0f;
+                const float ia = Q == 1 || q2 == 0 ? s_in[0][0] : s_in[Q - 1][0];
+                const float ib = Q == 1 || q2 == 0 ? s_in[0][1] : s_in[Q - 1][1];
                 cx v[R1];
 #pragma unroll
-                for (int j1 = 0; j1 < R1; ++j1) {
-                    const float pw = pre_l[M1 * j1 + m];
-                    v[j1] = cx{xa[i][j1] * (pw * sa), xb[i][j1] * (pw * sb)};
+                for (int j1 = 0; j1 < R1; ++j1) v[j1] = cx{xa[i][j1] * ia, xb[i][j1] * ib};
+                if (any_bad) {  // wave-uniform and rare: a non-finite trace enters as zeros
+                    const bool za = (bad_mask >> q2) & 1u, zb = (bad_mask >> (q2 + 1)) & 1u;
+#pragma unroll
+                    for (int j1 = 0; j1 < R1; ++j1) v[j1] = cx{za ? 0.0f : v[j1].x, zb ? 0.0f : v[j1].y};
                 }
                 p_pass1_round<P>(v, buf, t1l, m, ad.l1[i], on);
                 THZ_SCHED_FENCE();
@@ -474,6 +551,10 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                 const size_t p = p0 + 2 * (size_t)q;
                 const bool has2 = 2 * q + 1 < n_tr;
                 cx *bq = buf + q * WE;
+                // the split undoes each trace's scale (a zero trace's spectrum is +0.0: p_zero_if below)
+                const float o1s = q == 0 ? s_out[0][0] : s_out[Q - 1][0], o2s = q == 0 ? s_out[0][1] : s_out[Q - 1][1];
+                const bool z1 = q == 0 ? s_zero[0][0] : s_zero[Q - 1][0], z2 = q == 0 ? s_zero[0][1] : s_zero[Q - 1][1];
+                unsigned ym1 = 0u, ym2 = 0u;  // largest |component| of each masked spectrum (the inverse's PairScale)
                 FBUnwrap u1, u2;
 #pragma unroll 1
                 for (int g = 0; g < n_groups; ++g) {
@@ -490,8 +571,8 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                         const int km = kc == 0 ? 0 : N - kc;  // Z[N] = Z[0]
                         kcs[c] = kc;
                         const cx Fk = bq[kc], Fm = bq[km];
-                        X1[c] = cx{Fk.x + Fm.x, Fk.y - Fm.y};   // Z carries the factor 1/2 already (pre_s)
-                        X2[c] = cx{Fk.y + Fm.y, Fm.x - Fk.x};
+                        X1[c] = cx{(Fk.x + Fm.x) * o1s, (Fk.y - Fm.y) * o1s};   // Z carries the factor 1/2 already (pre_s)
+                        X2[c] = cx{(Fk.y + Fm.y) * o2s, (Fm.x - Fk.x) * o2s};
                         if constexpr (CM) h[c] = reinterpret_cast<const cx *>(mask_l)[kc];
                         else m[c] = mask_l[kc];
                         // real input: DC / Nyquist bins are real, with a POSITIVE zero as imaginary part (realfft writes
@@ -499,8 +580,8 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                         // float select left -0.0 = -0.5 (x - x) standing in the 10 x 10 x 10 instantiation
                         {
                             const bool real_bin = kc == 0 || ((N & 1) == 0 && kc == NF - 1);
-                            X1[c].y = p_zero_if(X1[c].y, real_bin);
-                            X2[c].y = p_zero_if(X2[c].y, real_bin);
+                            X1[c] = cx{p_zero_if(X1[c].x, z1), p_zero_if(X1[c].y, real_bin || z1)};
+                            X2[c] = cx{p_zero_if(X2[c].x, z2), p_zero_if(X2[c].y, real_bin || z2)};
                             rb[c] = real_bin;
                         }
                     }
@@ -524,11 +605,11 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                                            A.amp_out ? A.amp_out + o1 + NF : nullptr, A.ph_out ? A.ph_out + o1 + NF : nullptr);
                     }
                     if constexpr (SUMS) sums.group(g, 1, u2, has2, lane);
-                    // input of the inverse, in place: conj(G[k]) and conj(G[N-k]) of G = Y1full + i Y2full
-                    // (Yfull[n] = Y[n] up to N/2, conj(Y[N-n]) above) — bin k's owner is the only reader of
-                    // slots k and N-k
+                    // the masked spectra, unpacked in place until both scales are known (p_pack_inverse): Y1[k] in
+                    // slot k, Y2[k] in slot N-k; a real bin (DC, Nyquist) holds (Y1, Y2) in its one slot — bin k's
+                    // owner is the only reader of slots k and N-k
                     if constexpr (MODE == kPipe) {
-                        // no contraction here: y = X m must round before the sums below, so that the inverse
+                        // no contraction here: y = X m must round before the sums of the packing, so that the inverse
                         // transforms exactly the spectrum that was stored (a later Filter(6 / 7) update re-runs k_p<inv>
                         // on the stored one and has to land on the same samples)
 #pragma clang fp contract(off)
@@ -539,11 +620,23 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                                 // the rounding noise of the split, which would leak into the first trace's samples)
                                 const cx y1 = CM ? Y1[c] : cx{X1[c].x * m[c], X1[c].y * m[c]};
                                 const cx y2 = !has2 ? cx{0.0f, 0.0f} : CM ? Y2[c] : cx{X2[c].x * m[c], X2[c].y * m[c]};
+                                ym1 = umax(ym1, umax(abs_bits(y1.x), abs_bits(y1.y)));
+                                ym2 = umax(ym2, umax(abs_bits(y2.x), abs_bits(y2.y)));
                                 const int kc = kcs[c];
-                                bq[kc] = cx{y1.x - y2.y, -y1.y - y2.x};
-                                if (kc != 0 && 2 * kc != N) bq[N - kc] = cx{y1.x + y2.y, y1.y - y2.x};
+                                if (kc != 0 && 2 * kc != N) {
+                                    bq[kc] = y1;
+                                    bq[N - kc] = y2;
+                                } else {
+                                    bq[kc] = cx{y1.x, y2.x};
+                                }
                             }
                     }
+                }
+                if constexpr (MODE == kPipe) {
+                    const PairScale e1(wave_reduce_max_u32(ym1)), e2(wave_reduce_max_u32(ym2));
+                    p_pack_inverse<N, NF>(bq, lb4, e1, e2);
+                    if (q == 0) { i_out[0][0] = e1.out; i_out[0][1] = e2.out; }
+                    else { i_out[Q - 1][0] = e1.out; i_out[Q - 1][1] = e2.out; }
                 }
             }
             wave_sync();
@@ -566,19 +659,27 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                     y1v[i] = ld_off(f1, kc);
                     y2v[i] = ld_off(f1, has2 ? (unsigned)NF + kc : kc);
                 }
+                unsigned ym1 = 0u, ym2 = 0u;
 #pragma unroll
                 for (int i = 0; i < KI; ++i) {
                     const int k = lb1 + kWave * i;
-                    if (k < NF) {
-                        cx y1 = y1v[i];
-                        cx y2 = has2 ? y2v[i] : cx{0.0f, 0.0f};
-                        if (k == 0 || ((N & 1) == 0 && k == NF - 1)) {
-                            y1.y = 0.0f;
-                            y2.y = 0.0f;
-                        }
-                        bq[k] = cx{y1.x - y2.y, -y1.y - y2.x};
-                        if (k != 0 && 2 * k != N) bq[N - k] = cx{y1.x + y2.y, y1.y - y2.x};
+                    if (!has2) y2v[i] = cx{0.0f, 0.0f};
+                    if (k == 0 || ((N & 1) == 0 && k == NF - 1)) {
+                        y1v[i].y = 0.0f;
+                        y2v[i].y = 0.0f;
                     }
+                    if (k < NF) {
+                        ym1 = umax(ym1, umax(abs_bits(y1v[i].x), abs_bits(y1v[i].y)));
+                        ym2 = umax(ym2, umax(abs_bits(y2v[i].x), abs_bits(y2v[i].y)));
+                    }
+                }
+                const PairScale e1(wave_reduce_max_u32(ym1)), e2(wave_reduce_max_u32(ym2));
+                if (q == 0) { i_out[0][0] = e1.out; i_out[0][1] = e2.out; }
+                else { i_out[Q - 1][0] = e1.out; i_out[Q - 1][1] = e2.out; }
+#pragma unroll
+                for (int i = 0; i < KI; ++i) {
+                    const int k = lb1 + kWave * i;
+                    if (k < NF) p_pack_bin<N>(bq, k, y1v[i], y2v[i], e1, e2);
                 }
             }
             wave_sync();
@@ -606,6 +707,8 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
             const cx *bq = buf + q * WE;
             float *o1 = A.data_out + p * (size_t)N;
             float acc1 = 0.0f, acc2 = 0.0f;
+            // each trace's scale is undone on the window: post[n] 2^e (exact)
+            const float w1 = q == 0 ? i_out[0][0] : i_out[Q - 1][0], w2 = q == 0 ? i_out[0][1] : i_out[Q - 1][1];
             // four consecutive samples per lane: 16-byte stores (rows are only 4-byte aligned: store_f4)
             constexpr int QUADS = (N + 3) / 4, QR = (QUADS + kWave - 1) / kWave;
 #pragma unroll
@@ -617,8 +720,8 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                     for (int c = 0; c < 4; ++c) {
                         const cx U = bq[n0 + c];
                         const float pw = post_l[n0 + c];
-                        v1[c] = by_nt(U.x) * pw;
-                        v2[c] = by_nt(-U.y) * pw;
+                        v1[c] = by_nt(U.x) * (pw * w1);
+                        v2[c] = by_nt(-U.y) * (pw * w2);
                         acc1 += v1[c] * v1[c];
                         acc2 += v2[c] * v2[c];
                     }
@@ -630,7 +733,7 @@ __global__ __launch_bounds__(p_max_threads<P>(Q)) void k_p(FBArgs A, PTables T)
                         if (n0 + c < N) {
                             const cx U = bq[n0 + c];
                             const float pw = post_l[n0 + c];
-                            const float a = by_nt(U.x) * pw, b = by_nt(-U.y) * pw;
+                            const float a = by_nt(U.x) * (pw * w1), b = by_nt(-U.y) * (pw * w2);
                             o1[n0 + c] = a;
                             acc1 += a * a;
                             if (has2) { o1[N + n0 + c] = b; acc2 += b * b; }

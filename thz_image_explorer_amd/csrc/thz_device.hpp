@@ -20,6 +20,8 @@ namespace thz {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+
 #ifndef THZ_EMU
 
 // Orders this wave's LDS traffic: everything written to LDS by any lane
@@ -134,6 +136,17 @@ __device__ __forceinline__ float wave_scan_add(float v)
 }
 // sum over the 64 lanes, result in every lane
 __device__ __forceinline__ float wave_reduce_add(float v) { return wave_bcast<kWave - 1>(wave_scan_add(v)); }
+// largest value over the 64 lanes, result in every lane (the scan above with max; lanes out of range read 0)
+__device__ __forceinline__ unsigned wave_reduce_max_u32(unsigned v)
+{
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));  // row_shr:1
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));  // row_shr:2
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));  // row_shr:4
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));  // row_shr:8
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true));  // row_bcast:15
+    v = umax(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true));  // row_bcast:31
+    return (unsigned)__builtin_amdgcn_readlane((int)v, kWave - 1);
+}
 
 #define THZ_DYN_LDS(name) extern __shared__ __align__(16) unsigned char name[]
 // waves per SIMD a kernel is compiled for (register budget 512 / n); nothing in the emulation
@@ -189,6 +202,15 @@ __device__ __forceinline__ float launder_f(float x)
 #define THZ_LAUNCH(kernel, grid, block, lds_bytes, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), (lds_bytes), (stream), __VA_ARGS__)
 
+#else  // THZ_EMU
+
+// the emulation's lanes exchange values through wave_shfl (hip_emu.h): a butterfly over the 64 lanes
+inline unsigned wave_reduce_max_u32(unsigned v)
+{
+    for (int m = 1; m < kWave; m <<= 1) v = umax(v, __builtin_bit_cast(unsigned, wave_shfl_xor(__builtin_bit_cast(float, v), m)));
+    return v;
+}
+
 #endif  // !THZ_EMU
 
 // ---- x / d for a loop-invariant divisor (the inverse transform's 1 / nt when nt is not a power of two, where
@@ -208,6 +230,31 @@ struct DivConst {
         const float q = x * rcp;
         const float r = __builtin_fmaf(-q, d, x);
         return __builtin_fmaf(r, rcp, q);
+    }
+};
+
+// ---- power-of-two equalisation of a packed pair (two real traces as one complex transform, z = x1 + i x2: the P and
+// chirp-z kernels).  Packed as they come, each trace's rounding error would scale with the LARGER trace of its pair;
+// scaled by 2^-e first (e: the exponent of the trace's own largest |value|), both enter at [1, 2), and the split
+// multiplies by 2^e again — exact, so a trace's outputs do not depend on its partner at all.
+// |value| bits: the unsigned maximum of (bits & 0x7fffffff) orders finite values by magnitude, puts Inf above them
+// and NaN on top (a float max would drop the NaN).
+__device__ __forceinline__ unsigned abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
+struct PairScale {
+    float in;    // multiplies the trace before packing: 2^-e; 1 for a zero trace; 0 for a non-finite one
+    float out;   // multiplies what the split hands back: 2^e; 0 for a zero trace, NaN for a non-finite one
+    bool zero;   // every value is +-0: outputs are written as +0.0
+    bool bad;    // an Inf or NaN among the values: the trace enters as zeros (its samples would poison the partner's)
+                 // and its outputs are NaN
+    // from the wave maximum of abs_bits() over the trace's values
+    __device__ __forceinline__ explicit PairScale(unsigned max_abs)
+    {
+        const int e = (int)(max_abs >> 23);
+        const int c = e < 1 ? 1 : (e > 253 ? 253 : e);  // denormal maxima scale by 2^126, the largest by 2^-126
+        zero = max_abs == 0u;
+        bad = e == 255;
+        in = zero ? 1.0f : (bad ? 0.0f : __builtin_bit_cast(float, (unsigned)(254 - c) << 23));
+        out = zero ? 0.0f : (bad ? __builtin_nanf("") : __builtin_bit_cast(float, (unsigned)c << 23));
     }
 };
 
