@@ -623,7 +623,8 @@ typedef struct thz_group_session thz_group_session;
 int thz_group_session_create(thz_group *g, size_t nx, size_t ny, size_t nt, const float *time, float dx, float dy,
                              thz_group_session **out);
 void thz_group_session_destroy(thz_group_session *gs);
-/* the slab session of local member i (its buffers, plot copy-out, voxels ...); rows via thz_host_slab */
+/* the slab session of local member i (its buffers, plot copy-out ...); rows via thz_host_slab.  Its
+ * thz_session_voxels covers that slab only: the whole grid's 3-D view is thz_group_session_voxels. */
 thz_session *thz_group_session_member(thz_group_session *gs, int i);
 /* `cube`: the WHOLE (nx, ny, nt) host cube — each member uploads its rows — or NULL when the caller filled
  * the members' THZ_BUF_RAW itself.  Collective (C2 of the raw pixel sums). */
@@ -762,6 +763,21 @@ int thz_voxel_instances(thz_ctx *ctx, const float *d_opacity, size_t gw, size_t 
 int thz_session_voxels(thz_session *s, const thz_voxel_cfg *cfg, uint64_t max_instances, int scaling,
                        size_t orig_w, size_t orig_h, size_t orig_d, thz_voxel_instance *host_out,
                        uint64_t capacity, uint64_t *count, float *threshold, float *cube_dims);
+/* The same over the WHOLE grid of a group session (thz_group_session_grid), bit for bit what one session over the
+ * same cube and chain gives: the same threshold, the same *count, the same first min(count, capacity) records.
+ * thz_session_voxels on a group's member stays what it is: that slab alone, placed as though it were the whole grid.
+ * Collective and blocking, like thz_group_session_recompute: every rank calls it with the same cfg, max_instances,
+ * scaling and orig_*.  Every member computes the opacities of its slab of the final cube (the group's Deconvolution
+ * stage included; resident as its THZ_BUF_OPACITY); the max_instances-th largest value of the whole grid is found
+ * from all-reduced select histograms (thz_kth_largest's walk, on every rank); one all-reduce of the slabs' counts
+ * places each slab's records in the whole list; the records that fit are gathered to rank 0 in rank order.
+ * *count (the whole grid's), *threshold and cube_dims reach every rank; only the process that drives rank 0 receives
+ * records — its `capacity` is the one that counts (NULL with 0: count only); elsewhere host_out and capacity are
+ * ignored.  THZ_ERR_NOT_READY before the first recompute.  Every rank returns the same code: a failure on one rank
+ * (capacity without a buffer on rank 0's process, an allocation, the opacity launch) is agreed on by an all-reduce. */
+int thz_group_session_voxels(thz_group_session *gs, const thz_voxel_cfg *cfg, uint64_t max_instances, int scaling,
+                             size_t orig_w, size_t orig_h, size_t orig_d, thz_voxel_instance *host_out,
+                             uint64_t capacity, uint64_t *count, float *threshold, float *cube_dims);
 
 /* Per-stage device time of the most recent call of each kind, the value the
  * reference shows next to each filter (filter.rs:607-621).  `stage` is one

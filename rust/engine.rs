@@ -354,20 +354,21 @@ impl GpuEngine {
         t
     }
 
-    /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) of
-    /// local member 0's slab — the whole cube on one GPU.  `InstanceData` and `ThzVoxelInstance` share their layout.
+    /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
+    /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
+    /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and
+    /// `ThzVoxelInstance` share their layout.
     pub fn voxels(&self, cfg: &ThzVoxelCfg, max_instances: u64, scaling: usize, orig: (usize, usize, usize))
                   -> Option<(Vec<ThzVoxelInstance>, f32, [f32; 3])> {
         if self.session.is_null() { return None; }
         unsafe {
-            let s = thz_group_session_member(self.session, 0);
             let (mut n, mut thr, mut dims) = (0u64, 0f32, [0f32; 3]);
-            if thz_session_voxels(s, cfg, max_instances, scaling as c_int, orig.0, orig.1, orig.2, ptr::null_mut(), 0, &mut n, &mut thr, dims.as_mut_ptr()) != THZ_OK {
+            if thz_group_session_voxels(self.session, cfg, max_instances, scaling as c_int, orig.0, orig.1, orig.2, ptr::null_mut(), 0, &mut n, &mut thr, dims.as_mut_ptr()) != THZ_OK {
                 return None;
             }
             let mut out: Vec<ThzVoxelInstance> = Vec::with_capacity(n as usize);
             let cap = n;
-            if thz_session_voxels(s, cfg, max_instances, scaling as c_int, orig.0, orig.1, orig.2, out.as_mut_ptr(), cap, &mut n, &mut thr, dims.as_mut_ptr()) != THZ_OK {
+            if thz_group_session_voxels(self.session, cfg, max_instances, scaling as c_int, orig.0, orig.1, orig.2, out.as_mut_ptr(), cap, &mut n, &mut thr, dims.as_mut_ptr()) != THZ_OK {
                 return None;
             }
             out.set_len(n.min(cap) as usize);

@@ -216,6 +216,8 @@ SYMBOLS = [
     ("thz_session_plot", C.c_int, [_P, _SZ, _SZ, C.POINTER(PlotOut)]),
     ("thz_session_voxels", C.c_int, [_P, C.POINTER(VoxelCfg), C.c_uint64, C.c_int, _SZ, _SZ, _SZ, _P, C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_float), _P]),
+    ("thz_group_session_voxels", C.c_int, [_P, C.POINTER(VoxelCfg), C.c_uint64, C.c_int, _SZ, _SZ, _SZ, _P,
+                                           C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float), _P]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -685,6 +687,25 @@ class GroupSession:
             out = np.empty((nf, 2) if which == BUF_AVG_FFT else (nf,), np.float32)
             self.g._check(self.g.lib.thz_group_session_download(self.h, which, 0, 1, out.ctypes.data))
         return out
+
+    def voxels(self, cfg: "VoxelCfg", max_instances=VOXEL_MAX_INSTANCES, scaling=1, orig_dims=None, capacity=None):
+        """the 3-D tab's instances over the WHOLE grid (collective: every rank calls it) ->
+        (instances, threshold, (cube_width, cube_height, cube_depth), count).  Only the process that drives rank 0
+        receives instances; elsewhere the array is empty.  count is the whole grid's."""
+        lib = self.g.lib
+        orig = orig_dims or (self.nx, self.ny, self.member(0).nt_out)
+        root = 0 in self.g.ranks
+        n, thr = C.c_uint64(), C.c_float()
+        dims = np.zeros(3, np.float32)
+        if capacity is None:   # count first
+            self.g._check(lib.thz_group_session_voxels(self.h, C.byref(cfg), max_instances, scaling, orig[0], orig[1],
+                                                       orig[2], None, 0, C.byref(n), C.byref(thr), dims.ctypes.data))
+            capacity = n.value
+        out = np.zeros(capacity if root else 0, VOXEL_INSTANCE)
+        self.g._check(lib.thz_group_session_voxels(self.h, C.byref(cfg), max_instances, scaling, orig[0], orig[1],
+                                                   orig[2], out.ctypes.data if out.size else None, out.size,
+                                                   C.byref(n), C.byref(thr), dims.ctypes.data))
+        return out[:min(n.value, out.size)], thr.value, tuple(float(x) for x in dims), n.value
 
     def close(self):
         if self.h:

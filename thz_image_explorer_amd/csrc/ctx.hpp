@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -225,3 +226,16 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
 // api.cpp: order-free column sums over all rows (d_list null) or over the listed rows of d_arr
 int pixel_sum_rows(thz_ctx *ctx, const float *d_arr, const uint32_t *d_list, size_t npix, size_t L, float *d_out);
 
+
+// voxel_api.cpp: the three-level radix-select walk of thz_kth_largest.  hist(level, prefix, h) leaves in h[kSelBins]
+// the level's histogram over ALL the values (one GPU's, or a group's all-reduced one: every rank walks the same
+// histograms to the same bins, the retry of level 0 with floor 0 included).  *too_few: the histograms hold fewer
+// than k values (THZ_ERR_INVALID); any other error is hist's.
+int select_walk(uint64_t k, const std::function<int(int, uint32_t, uint64_t *)> &hist, float *out, bool *too_few);
+// voxel_api.cpp: thz_voxel_instances in two halves, so that a group can exchange the tiles' counts in between.
+// voxel_count_scan enqueues the per-trace counts and their scan into the context's workspace and leaves the tile's
+// total at *d_total (device, in that workspace); voxel_emit writes the first `capacity` records of the tile from
+// the same workspace (nothing may use it in between).
+int voxel_count_scan(thz_ctx *ctx, const float *d_opacity, size_t npix, size_t gd, float threshold, uint64_t **d_total);
+int voxel_emit(thz_ctx *ctx, const float *d_opacity, size_t npix, size_t gh, size_t gd, const VoxelGeom &g,
+               thz_voxel_instance *d_out, uint64_t capacity);

@@ -3,6 +3,8 @@
 #include "host_windows.hpp"
 
 #include <cstring>
+#include <functional>
+#include <vector>
 
 using namespace thz;
 
@@ -17,7 +19,79 @@ inline float key_to_float(uint32_t key)
     return f;
 }
 
+// workspace of the instance loop: counts u32[npix] | offsets u64[npix] | tile sums u64[ntiles] | total u64
+struct VoxelWs {
+    uint32_t *counts;
+    unsigned long long *offsets, *tiles, *total;
+};
+
+int voxel_ws(thz_ctx *ctx, size_t npix, VoxelWs *w)
+{
+    const size_t ntiles = (npix + 2047) / 2048;
+    const size_t off_offsets = (npix * sizeof(uint32_t) + 15) & ~(size_t)15;
+    const size_t off_tiles = off_offsets + npix * sizeof(uint64_t);
+    const size_t off_total = off_tiles + ntiles * sizeof(uint64_t);
+    if (int rc = ensure_ws(ctx, off_total + sizeof(uint64_t))) return rc;
+    char *ws = static_cast<char *>(ctx->ws);
+    w->counts = reinterpret_cast<uint32_t *>(ws);
+    w->offsets = reinterpret_cast<unsigned long long *>(ws + off_offsets);
+    w->tiles = reinterpret_cast<unsigned long long *>(ws + off_tiles);
+    w->total = reinterpret_cast<unsigned long long *>(ws + off_total);
+    return THZ_OK;
+}
+
 }  // namespace
+
+int select_walk(uint64_t k, const std::function<int(int, uint32_t, uint64_t *)> &hist, float *out, bool *too_few)
+{
+    *too_few = false;
+    std::vector<uint64_t> h(kSelBins);
+    int bins[3] = {0, 0, 0};
+    uint32_t prefix = 0;
+    uint64_t rank = k;
+    // level 0 first with everything below 2^-10 lumped into one bin (cheap: long runs); the
+    // full histogram only if the k-th largest turns out to be that small
+    uint32_t floor_bin = (0x80000000u | 0x3A800000u) >> 21;
+    for (int level = 0; level < 3; ++level) {
+        for (;;) {
+            if (int rc = hist(level, level == 0 ? floor_bin : prefix, h.data())) return rc;
+            uint64_t r = 0;
+            if (thz_host_select_step(h.data(), level == 2 ? 1024 : kSelBins, rank, &bins[level], &r)) {
+                *too_few = true;
+                return THZ_ERR_INVALID;
+            }
+            if (level == 0 && floor_bin != 0 && (uint32_t)bins[0] == floor_bin) {
+                floor_bin = 0;
+                continue;
+            }
+            rank = r;
+            break;
+        }
+        prefix = level == 0 ? (uint32_t)bins[0] : (((uint32_t)bins[0] << 11) | (uint32_t)bins[1]);
+    }
+    *out = thz_host_select_value(bins[0], bins[1], bins[2]);
+    return THZ_OK;
+}
+
+int voxel_count_scan(thz_ctx *ctx, const float *d_opacity, size_t npix, size_t gd, float threshold, uint64_t **d_total)
+{
+    VoxelWs w;
+    if (int rc = voxel_ws(ctx, npix, &w)) return rc;
+    launch_voxel_count(ctx->stream, npix, (int)gd, d_opacity, threshold, w.counts);
+    launch_scan_counts(ctx->stream, w.counts, npix, w.tiles, w.offsets, w.total);
+    *d_total = reinterpret_cast<uint64_t *>(w.total);
+    return check_launch(ctx);
+}
+
+int voxel_emit(thz_ctx *ctx, const float *d_opacity, size_t npix, size_t gh, size_t gd, const VoxelGeom &g,
+               thz_voxel_instance *d_out, uint64_t capacity)
+{
+    VoxelWs w;
+    if (int rc = voxel_ws(ctx, npix, &w)) return rc;
+    launch_voxel_emit(ctx->stream, npix, (int)gd, gh, d_opacity, w.counts, w.offsets, g, reinterpret_cast<float *>(d_out),
+                      capacity);
+    return check_launch(ctx);
+}
 
 extern "C" {
 
@@ -101,34 +175,20 @@ int thz_kth_largest(thz_ctx *ctx, const float *d_vals, size_t n, uint64_t k, flo
     if (int rc = use_device(ctx)) return rc;
     if (int rc = ensure_ws(ctx, kSelBins * sizeof(uint64_t))) return rc;
     uint64_t *d_hist = static_cast<uint64_t *>(ctx->ws);
-    std::vector<uint64_t> hist(kSelBins);
     StageTimer t(ctx, THZ_STAGE_VOXEL_SELECT);
-    int bins[3] = {0, 0, 0};
-    uint32_t prefix = 0;
-    uint64_t rank = k;
-    // level 0 first with everything below 2^-10 lumped into one bin (cheap: long runs); the
-    // full histogram only if the k-th largest turns out to be that small
-    uint32_t floor_bin = (0x80000000u | 0x3A800000u) >> 21;
-    for (int level = 0; level < 3; ++level) {
-        for (;;) {
+    bool too_few = false;
+    const int rc = select_walk(
+        k,
+        [&](int level, uint32_t prefix, uint64_t *hist) -> int {
             HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, kSelBins * sizeof(uint64_t), ctx->stream));
-            if (int rc = thz_select_histogram(ctx, d_vals, n, level, level == 0 ? floor_bin : prefix, d_hist)) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(hist.data(), d_hist, kSelBins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            if (int rc2 = thz_select_histogram(ctx, d_vals, n, level, prefix, d_hist)) return rc2;
+            HIP_TRY(ctx, hipMemcpyAsync(hist, d_hist, kSelBins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            uint64_t r = 0;
-            if (thz_host_select_step(hist.data(), level == 2 ? 1024 : kSelBins, rank, &bins[level], &r))
-                return fail(ctx, THZ_ERR_INVALID, "thz_kth_largest: histogram holds fewer than k values");
-            if (level == 0 && floor_bin != 0 && (uint32_t)bins[0] == floor_bin) {
-                floor_bin = 0;
-                continue;
-            }
-            rank = r;
-            break;
-        }
-        prefix = level == 0 ? (uint32_t)bins[0] : (((uint32_t)bins[0] << 11) | (uint32_t)bins[1]);
-    }
-    *out = thz_host_select_value(bins[0], bins[1], bins[2]);
-    return THZ_OK;
+            return THZ_OK;
+        },
+        out, &too_few);
+    if (too_few) return fail(ctx, THZ_ERR_INVALID, "thz_kth_largest: histogram holds fewer than k values");
+    return rc;
 }
 
 int thz_voxel_threshold(thz_ctx *ctx, const float *d_opacity, size_t n, uint64_t max_instances, float *out)
@@ -161,25 +221,11 @@ int thz_voxel_instances(thz_ctx *ctx, const float *d_opacity, size_t gw, size_t 
     *count = 0;
     const size_t npix = gw * gh;
     if (npix == 0) return THZ_OK;
-    // workspace: counts u32[npix] | offsets u64[npix] | tile sums u64[ntiles] | total u64
-    const size_t ntiles = (npix + 2047) / 2048;
-    const size_t off_counts = 0;
-    const size_t off_offsets = (npix * sizeof(uint32_t) + 15) & ~(size_t)15;
-    const size_t off_tiles = off_offsets + npix * sizeof(uint64_t);
-    const size_t off_total = off_tiles + ntiles * sizeof(uint64_t);
-    if (int rc = ensure_ws(ctx, off_total + sizeof(uint64_t))) return rc;
-    char *ws = static_cast<char *>(ctx->ws);
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(ws + off_counts);
-    unsigned long long *d_offsets = reinterpret_cast<unsigned long long *>(ws + off_offsets);
-    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(ws + off_tiles);
-    unsigned long long *d_total = reinterpret_cast<unsigned long long *>(ws + off_total);
-    VoxelGeom g{L.spacing_w, L.spacing_h, L.spacing_d, L.half_w, L.half_h, L.half_d, (float)scaling, threshold, x0};
+    const VoxelGeom g{L.spacing_w, L.spacing_h, L.spacing_d, L.half_w, L.half_h, L.half_d, (float)scaling, threshold, x0};
     StageTimer t(ctx, THZ_STAGE_VOXEL_EMIT);
-    launch_voxel_count(ctx->stream, npix, (int)gd, d_opacity, threshold, d_counts);
-    launch_scan_counts(ctx->stream, d_counts, npix, d_tiles, d_offsets, d_total);
-    launch_voxel_emit(ctx->stream, npix, (int)gd, gh, d_opacity, d_counts, d_offsets, g, reinterpret_cast<float *>(d_out),
-                      capacity);
-    if (int rc = check_launch(ctx)) return rc;
+    uint64_t *d_total = nullptr;
+    if (int rc = voxel_count_scan(ctx, d_opacity, npix, gd, threshold, &d_total)) return rc;
+    if (int rc = voxel_emit(ctx, d_opacity, npix, gh, gd, g, d_out, capacity)) return rc;
     unsigned long long total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -331,6 +331,25 @@ std::vector<float> GpuEngine::time_out() const
     if (session_ && !t.empty()) thz_session_time_out(thz_group_session_member(session_, 0), t.data());
     return t;
 }
+bool GpuEngine::voxels(const thz_voxel_cfg &cfg, uint64_t max_instances, size_t scaling, size_t orig_w, size_t orig_h,
+                       size_t orig_d, std::vector<thz_voxel_instance> &out, float &threshold, float cube_dims[3])
+{
+    out.clear();
+    if (!session_) return false;
+    uint64_t n = 0;
+    if (thz_group_session_voxels(session_, &cfg, max_instances, (int)scaling, orig_w, orig_h, orig_d, nullptr, 0, &n,
+                                 &threshold, cube_dims) != THZ_OK)
+        return false;
+    out.resize((size_t)n);
+    const uint64_t cap = n;
+    if (thz_group_session_voxels(session_, &cfg, max_instances, (int)scaling, orig_w, orig_h, orig_d,
+                                 cap ? out.data() : nullptr, cap, &n, &threshold, cube_dims) != THZ_OK) {
+        out.clear();
+        return false;
+    }
+    out.resize((size_t)(n < cap ? n : cap));
+    return true;
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;

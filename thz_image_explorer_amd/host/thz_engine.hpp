@@ -64,6 +64,10 @@ public:
     bool roi(const std::string &uuid, const thz_roi_out &out);
     size_t nt_out() const;
     std::vector<float> time_out() const;
+    // the 3-D tab's instances over the WHOLE grid (thz_group_session_voxels; data_thread.rs:82-101): threshold from
+    // the whole cube, every slab's instances in x, y, z order — what one GPU gives for the same cube
+    bool voxels(const thz_voxel_cfg &cfg, uint64_t max_instances, size_t scaling, size_t orig_w, size_t orig_h,
+                size_t orig_d, std::vector<thz_voxel_instance> &out, float &threshold, float cube_dims[3]);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
