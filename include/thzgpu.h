@@ -617,8 +617,10 @@ typedef enum thz_gather {
  * does shards (round 3): a non-zero tilt (the plan is made for the whole grid), scale_factor > 1 (a block of s x s
  * pixels whose rows lie in two slabs belongs to the slab that holds its LAST row: the slab in front hands over the
  * partial sums of its rows, the sum continues in the reference's order — THZ_ERR_UNSUPPORTED only when a slab has
- * fewer rows than the scale factor), want_means 2 (the reference's sequential means, slab after slab on a carried
- * running sum: bit for bit one session's, serial by construction). */
+ * fewer rows than the scale factor: nx / world < scale_factor while nx / scale_factor and ny / scale_factor are not 0;
+ * every rank refuses before any exchange and the outputs stay those of the last recompute), want_means 2 (the
+ * reference's sequential means, slab after slab on a carried running sum: bit for bit one session's, serial by
+ * construction). */
 typedef struct thz_group_session thz_group_session;
 int thz_group_session_create(thz_group *g, size_t nx, size_t ny, size_t nt, const float *time, float dx, float dy,
                              thz_group_session **out);

@@ -264,3 +264,102 @@ def test_rank_processes_halo_paths(engine, tmp_path, world, shape, variant):
             assert np.array_equal(got, res[0][f"{name}_rank0"]), (name, r)
         assert int(res[r][f"roi_count_rank{r}"][0]) == want_roi["count"]
         assert rel(res[r][f"roi_amp_rank{r}"], want_roi["signal_fft"]) < 2e-6
+
+
+def test_rank_processes_smallest_admitted_slabs(engine, tmp_path):
+    """world 3, nx 10, scale factor 3: slabs of 4, 3 and 3 rows — the smallest the rule of include/thzgpu.h admits — and
+    both slab edges inside a block, so the partial block sums travel rank 0 -> 1 -> 2"""
+    import thz_image_explorer_amd as pkg
+    assert [pkg.host_slab(10, 3, q)[1] for q in range(3)] == [4, 3, 3]
+    test_rank_processes_halo_paths(engine, tmp_path, 3, (10, 6, 256), "scale3")
+
+
+REFUSE_SCRIPT = textwrap.dedent('''
+    import os, sys, time
+    sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+    import numpy as np
+    import thz_image_explorer_amd as pkg
+    import synth
+    rank, world, uid_file, out_file = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
+    nx, ny, nt = {shape!r}
+    if rank == 0:
+        uid = pkg.group_unique_id()
+        with open(uid_file + ".tmp", "wb") as f:
+            f.write(uid)
+        os.rename(uid_file + ".tmp", uid_file)
+    else:
+        for _ in range(3000):
+            if os.path.exists(uid_file):
+                break
+            time.sleep(0.01)
+        uid = open(uid_file, "rb").read()
+    time_axis, cube = synth.make_cube(nx, ny, nt)
+    res = {{}}
+    with pkg.Group(device=0, rank=rank, world=world, uid=uid) as g:
+        gs = pkg.GroupSession(g, nx, ny, time_axis, 0.5, 0.5)
+        try:
+            gs.upload(cube, subtract_bias=False)
+            cfg = pkg.chain_cfg_default(time_axis)
+            cfg.scale_factor = {sf!r}
+            code = 0
+            try:
+                gs.recompute(cfg, 1, pkg.GATHER_ALL)
+            except pkg.ThzError as e:
+                code = e.code
+            res["code_rank%d" % rank] = np.array([code])
+            # every rank refused before any exchange: the ranks are still in step for the unscaled chain
+            cfg.scale_factor = 1
+            gs.recompute(cfg, 1, pkg.GATHER_ALL)
+            res["avg_amp_rank%d" % rank] = gs.member(0).download(pkg.BUF_AVG_AMPLITUDES)
+            if rank == 0:
+                for name, w in (("img", pkg.BUF_IMG), ("data", pkg.BUF_DATA), ("fft", pkg.BUF_FFT)):
+                    res[name] = gs.download(w)
+        finally:
+            gs.close()
+    np.savez(out_file, **res)
+''')
+
+
+def test_rank_processes_refuse_a_short_slab_together(engine, tmp_path):
+    """world 3, nx 5, scale factor 3 (slabs of 2, 2 and 1 rows): every rank process refuses the recompute with
+    THZ_ERR_UNSUPPORTED before any exchange — none waits in a send or receive the others never make — and the group
+    stays usable: the unscaled chain that follows is one session's"""
+    import synth
+    import thz_image_explorer_amd as pkg
+    from test_gpu_parity import rel
+    _build_mock()
+    world, shape, sf = 3, (5, 6, 256), 3
+    nx, ny, nt = shape
+    assert [pkg.host_slab(nx, world, q)[1] for q in range(world)] == [2, 2, 1]
+    time_axis, cube = synth.make_cube(nx, ny, nt)
+    s = pkg.Session(engine, nx, ny, time_axis, 0.5, 0.5)
+    try:
+        s.upload(cube, subtract_bias=False)
+        s.recompute(pkg.chain_cfg_default(time_axis))
+        want = {n: s.download(w) for n, w in (("img", pkg.BUF_IMG), ("data", pkg.BUF_DATA), ("fft", pkg.BUF_FFT),
+                                              ("avg_amp", pkg.BUF_AVG_AMPLITUDES))}
+    finally:
+        s.close()
+    script = tmp_path / "rank.py"
+    script.write_text(REFUSE_SCRIPT.format(root=ROOT, tests=HERE, shape=shape, sf=sf))
+    uid_file = str(tmp_path / "uid.bin")
+    env = dict(os.environ, THZ_RCCL_LIB=MOCK, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    procs = [subprocess.Popen([sys.executable, str(script), str(r), str(world), uid_file, str(tmp_path / f"out{r}.npz")], env=env,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            o, _ = p.communicate(timeout=240)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()          # the exact children started above
+            pytest.fail("a rank process did not finish: the ranks did not refuse together")
+        outs.append(o)
+    for r, (p, o) in enumerate(zip(procs, outs)):
+        assert p.returncode == 0, f"rank {r}:\n{o[-3000:]}"
+    res = [np.load(str(tmp_path / f"out{r}.npz")) for r in range(world)]
+    for r in range(world):
+        assert int(res[r][f"code_rank{r}"][0]) == -2, r          # THZ_ERR_UNSUPPORTED on every rank
+        assert rel(res[r][f"avg_amp_rank{r}"], want["avg_amp"]) < 2e-6, r
+    for name in ("img", "data", "fft"):
+        assert np.array_equal(res[0][name], want[name]), name

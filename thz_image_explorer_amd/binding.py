@@ -654,7 +654,9 @@ class GroupSession:
         self.g._check(self.g.lib.thz_group_session_set_rois(self.h, n, counts, flat.ctypes.data if flat.size else None))
 
     def roi(self, index, want=None, nt_out=None):
-        res, cnt, ro = _roi_out(self.nt if nt_out is None else nt_out, want)
+        """per-region vectors of the last recompute -> dict (+ 'count'); sized like the chain's output traces (a
+        tilt extends them) unless nt_out says otherwise"""
+        res, cnt, ro = _roi_out(self.member(0).nt_out if nt_out is None else nt_out, want)
         self.g._check(self.g.lib.thz_group_session_roi(self.h, index, C.byref(ro)))
         res["count"] = cnt.value
         return res
@@ -675,8 +677,9 @@ class GroupSession:
         return nx.value, ny.value
 
     def download(self, which, nt_out=None):
-        """gathered buffer of rank 0 (whole grid) or a pixel-mean vector"""
-        nto = self.nt if nt_out is None else nt_out
+        """gathered buffer of rank 0 (whole grid) or a pixel-mean vector; traces and spectra are sized like the
+        chain's output traces (a tilt extends them) unless nt_out says otherwise"""
+        nto = self.member(0).nt_out if nt_out is None else nt_out
         nf = nto // 2 + 1
         per = {BUF_FFT: (nf, 2), BUF_AMPLITUDES: (nf,), BUF_PHASES: (nf,), BUF_DATA: (nto,), BUF_IMG: ()}
         if which in per:

@@ -602,7 +602,11 @@ int thz_group_session_recompute(thz_group_session *gs, const thz_chain_cfg *cfg,
     // block it cannot finish and hands the partial sums to the next slab, which continues the sequence — the block
     // belongs to the slab that holds its LAST row.  Needed only when the walk re-runs the scaling stage.
     const size_t sf = cfg->scale_factor > 1 ? (size_t)cfg->scale_factor : 1;
-    if (!single && sf > 1) {
+    // A slab shorter than the scale factor is refused by a rule of (nx, ny, world, sf) alone: every rank refuses
+    // here, before any exchange and before any slab is touched, and the group keeps its last outputs
+    if (slab_scale_refused(gs->nx, gs->ny, g->world, sf))
+        return gfail(g, THZ_ERR_UNSUPPORTED, "scaling over slabs: a slab has fewer rows than the scale factor");
+    if (!single && sf > 1 && gs->nx / sf > 0 && gs->ny / sf > 0) {
         std::vector<const float *> out_c;
         std::vector<float *> in;
         for (size_t i = 0; i < gs->sess.size(); ++i) {

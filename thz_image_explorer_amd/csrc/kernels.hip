@@ -813,6 +813,8 @@ __global__ __launch_bounds__(64) void k_gather_sum_w(const float *__restrict__ a
                                                      const float *__restrict__ w1, const float *__restrict__ w2,
                                                      const float *__restrict__ w3, float *__restrict__ out)
 {
+#pragma clang fp contract(off)
+    // (the multiplies and the adds round one by one: roi_data is the reference's bit for bit)
     const size_t z = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (z >= len) return;
     const float *col = arr + z;
@@ -859,6 +861,7 @@ __global__ __launch_bounds__(256) void k_scale_rows_partial(const float *__restr
 __global__ __launch_bounds__(256) void k_div_vec(const float *__restrict__ in, const float *__restrict__ w, float d, size_t n,
                                                  float *__restrict__ out)
 {
+#pragma clang fp contract(off)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         out[i] = (w ? in[i] * w[i] : in[i]) / d;
 }

@@ -96,8 +96,11 @@ struct SlabScale {
     size_t tail = 0;       // trailing raw rows that start a block the next slab completes (0: none, or beyond the block grid)
     size_t rows = 0;       // rows of the block grid this slab owns = head_valid + full
     size_t x0 = 0;         // ... and where they start in the block grid
-    bool ok = true;        // false: a slab shorter than the scale factor (a block would span three slabs)
 };
+// The one rule for scaling a grid of nx x ny cut into `world` slabs by sf, the same on every rank: refused when the
+// scaling is not the identity (sf > 1, nx / sf > 0, ny / sf > 0) and the smallest slab thz_host_slab cuts (nx / world
+// rows) is shorter than sf — a block would span three slabs.  slab_scale is only called for splits it admits.
+bool slab_scale_refused(size_t nx_total, size_t ny, int world, size_t sf);
 SlabScale slab_scale(size_t nx_total, int world, int rank, size_t sf);
 // before session_enqueue of a scaled group recompute: the partial sums of this slab's trailing block into d_carry_out
 int session_scale_tail(thz_session *s, const thz_chain_cfg *cfg);

@@ -181,6 +181,14 @@ static int session_tail(thz_session *s, const thz_chain_cfg *cfg)
     return thz_ifft(ctx, npix, s->d_fft, d_post, s->d_data, s->d_img);
 }
 
+bool slab_scale_refused(size_t nx_total, size_t ny, int world, size_t sf)
+{
+    if (sf <= 1 || nx_total / sf == 0 || ny / sf == 0 || world < 1) return false;  // the identity
+    return nx_total / (size_t)world < sf;
+}
+
+// Every slab holds at least sf rows (slab_scale_refused is false): a slab's leading rows finish at most one block
+// (head < sf <= n) and the next slab always holds the rest of its trailing block (tail < sf <= n1).
 SlabScale slab_scale(size_t nx_total, int world, int rank, size_t sf)
 {
     SlabScale r;
@@ -190,24 +198,16 @@ SlabScale slab_scale(size_t nx_total, int world, int rank, size_t sf)
         (void)thz_host_slab(nx_total, world, q, &x0, &n);
         SlabScale c;
         c.head = (sf - x0 % sf) % sf;
-        if (c.head > n) { c.ok = false; c.head = n; }
         c.head_valid = c.head > 0 && x0 / sf < nb;
         const size_t b0 = (x0 + c.head) / sf;  // first block that starts inside the slab
         c.full = b0 < nb ? (n - c.head) / sf : 0;
         if (b0 + c.full > nb) c.full = nb - b0;
         const size_t rest = n - c.head - c.full * sf;
         c.tail = (b0 + c.full < nb) ? rest : 0;
-        if (c.tail && q + 1 < world) {  // the next slab must hold the rest of that block
-            size_t x1 = 0, n1 = 0;
-            (void)thz_host_slab(nx_total, world, q + 1, &x1, &n1);
-            if (n1 < sf - c.tail) c.ok = false;
-        }
         c.rows = (c.head_valid ? 1 : 0) + c.full;
         c.x0 = acc;
         acc += c.rows;
-        const bool ok = r.ok && c.ok;
         r = c;
-        r.ok = ok;
     }
     return r;
 }
@@ -218,9 +218,10 @@ int session_scale_tail(thz_session *s, const thz_chain_cfg *cfg)
     s->carry_out_valid = false;
     const size_t sf = cfg->scale_factor > 1 ? (size_t)cfg->scale_factor : 1;
     if (sf <= 1 || !s->raw_grid_rows || s->ny / sf == 0 || s->raw_grid_rows / sf == 0) return THZ_OK;
+    if (slab_scale_refused(s->raw_grid_rows, s->ny, s->slab_world, sf))
+        return fail(ctx, THZ_ERR_UNSUPPORTED, "scaling over slabs: a slab has fewer rows than the scale factor");
     if (int rc = use_device(ctx)) return rc;
     const SlabScale sl = slab_scale(s->raw_grid_rows, s->slab_world, s->slab_rank, sf);
-    if (!sl.ok) return fail(ctx, THZ_ERR_UNSUPPORTED, "scaling over slabs: a slab has fewer rows than the scale factor");
     const size_t need = (s->ny / sf) * s->nt;
     if (s->carry_floats != need) {
         s->carry_floats = 0;
@@ -256,18 +257,19 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
 
     // ---- scaling (math_tools.rs:242-310): s x s block means of the raw cube, / s^2 also on ragged
     // edges; dx, dy grow by s; identity when s <= 1 or when a side would vanish (:244-256)
+    // (a group's slab: the WHOLE grid's sides decide, the same on every rank)
     size_t sf = cfg->scale_factor > 1 ? (size_t)cfg->scale_factor : 1;
-    if (s->nx / sf == 0 || s->ny / sf == 0) sf = 1;
+    const bool slab = s->raw_grid_rows != 0;
+    if ((slab ? s->raw_grid_rows : s->nx) / sf == 0 || s->ny / sf == 0) sf = 1;
     // ---- Tilt Compensation, planned before any buffer is touched: a length no transform exists for
     // leaves the session as it was (the reference re-plans for any length)
     // a group's slab: the rows of the CURRENT grid it owns and where they sit in the whole grid (the Tilt plan and
     // the regions of interest depend on the position in the whole grid); behind a scaling stage, slab_scale's split
     SlabScale sl;
-    const bool slab = s->raw_grid_rows != 0;
-    if (slab && s->raw_grid_rows / sf == 0) sf = 1;
     if (slab && sf > 1) {
+        if (slab_scale_refused(s->raw_grid_rows, s->ny, s->slab_world, sf))
+            return fail(ctx, THZ_ERR_UNSUPPORTED, "scaling over slabs: a slab has fewer rows than the scale factor");
         sl = slab_scale(s->raw_grid_rows, s->slab_world, s->slab_rank, sf);
-        if (!sl.ok) return fail(ctx, THZ_ERR_UNSUPPORTED, "scaling over slabs: a slab has fewer rows than the scale factor");
     }
     const size_t nx_c = slab && sf > 1 ? sl.rows : s->nx / sf, ny_c = s->ny / sf;
     const size_t g_rows = slab ? s->raw_grid_rows / sf : nx_c, g_x0 = slab ? (sf > 1 ? sl.x0 : s->raw_grid_x0) : 0;
@@ -371,8 +373,9 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // ---- multipliers in the reference's f32 order: ((tilt * td_before) * fft_window)
     std::vector<float> pre(nt_cur, 1.0f), w(nt_cur), post, mask(nf, 1.0f);
     // ... and one by one for the regions of interest's reference-order roi_data (session_roi.cpp): the mean of the
-    // fft stage's `data`, on which the reference performs the three multiplies in turn
-    const bool want_sep = cfg->want_means == 2 && !s->rois.empty();
+    // fft stage's `data`, on which the reference performs the three multiplies in turn.  Built whether or not regions
+    // are set: regions set later are summed by a tail-only recompute (chain position >= 6), which does not come here
+    const bool want_sep = cfg->want_means == 2;
     std::vector<float> sep(want_sep ? 3 * nt_cur : 0);
     s->wsep_on[0] = s->wsep_on[1] = s->wsep_on[2] = false;
     if (tilt_as_multiplier) {
