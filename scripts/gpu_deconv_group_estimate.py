@@ -1,5 +1,5 @@
 """Developer tool: what the Deconvolution stage would take on N GPUs, from phase times measured on ONE.
-The group runs the stage in phases (csrc/group_api.cpp): A transform + band energies of the rank's rows (per pixel:
+The group runs the stage in phases (csrc/group_deconv.cpp): A transform + band energies of the rank's rows (per pixel:
 1/N of the single-GPU time), B the Richardson-Lucy iterations of the rank's bands over the whole image (bands dealt
 out by cost, contiguous ranges), C recombination of the rank's rows (1/N).  B is measured here per rank by running
 thz_deconvolve with that rank's band range on the whole image and reading the "iterations" line of THZ_DEBUG_TIMING;
@@ -59,7 +59,7 @@ if __name__ == "__main__":
     cost = lambda lo, hi: alpha * max([table[k][0] for k in range(lo, hi)] + [0]) + beta * sum(table[k][0] * table[k][1] for k in range(lo, hi))
     plans = {}
     for world in (2, 4, 8):
-        # the ranges the library deals out (csrc/group_api.cpp: dynamic programme over the cut points on the model
+        # the ranges the library deals out (csrc/group_deconv.cpp, dc_band_ranges: dynamic programme over the cut points on the model
         # alpha x longest band's iterations + beta x sum of iterations x tiles)
         best = [[1e300] * (nb + 1) for _ in range(world + 1)]
         cut = [[0] * (nb + 1) for _ in range(world + 1)]

@@ -199,7 +199,7 @@ def test_production_size_three_wide_chains_vs_oracle(engine, monkeypatch):
 
 
 def _group_band_ranges(plan, members):
-    """the contiguous band ranges thz_group_session_deconvolve gives its members (group_api.cpp: alpha x longest band's
+    """the contiguous band ranges thz_group_session_deconvolve gives its members (dc_band_ranges in group_deconv.cpp: alpha x longest band's
     iterations + beta x iterations x tiles, the slowest member's cost minimised)"""
     bands = plan["bands"]
     nb = len(bands)

@@ -1,7 +1,7 @@
 """Two (and three) RANKS, one process each, through the library's process-per-GPU entry points — on ONE GPU.
 
 RCCL refuses two ranks on one device, so this test swaps RCCL for tests/mock_rccl (THZ_RCCL_LIB: the eleven entry
-points group_api.cpp resolves, with their real signatures, over shared memory and a process-shared barrier; test
+points group_comm.cpp resolves, with their real signatures, over shared memory and a process-shared barrier; test
 infrastructure, see its header).  Everything else is the real thing: thz_group_unique_id / thz_group_create_rank, one
 process per rank with its own HIP context, thz_group_session_upload / _recompute / _deconvolve / _download — the
 call sequence bench.py --gpus N and the Rust data threads make.  What it pins: who sends what to whom (grouped

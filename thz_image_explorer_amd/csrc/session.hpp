@@ -1,5 +1,5 @@
 // session.hpp — the resident-cube session behind thz_session* (session_api.cpp) and the pieces of its
-// recompute that the multi-GPU group (group_api.cpp) drives slab by slab.
+// recompute that the multi-GPU group (group_session.cpp) drives slab by slab.
 #pragma once
 #include "ctx.hpp"
 
@@ -68,7 +68,7 @@ struct thz_session {
     bool roi_src_fresh = false;    // the last session_roi_sums renewed the source block (a group all-reduces it then)
     int last_sf = -1, last_tilt_active = -1;
     double last_tilt_x = 0.0, last_tilt_y = 0.0;
-    // Placement in a group's grid (group_api.cpp).  raw_grid_rows == 0: the session is the whole grid.  Otherwise it
+    // Placement in a group's grid (group_session.cpp).  raw_grid_rows == 0: the session is the whole grid.  Otherwise it
     // holds rows raw_grid_x0 .. + nx of the raw_grid_rows rows of the RAW grid (slab `slab_rank` of `slab_world`, all
     // slabs cut by thz_host_slab), and session_enqueue derives grid_x0 / grid_rows: the same for the CURRENT grid —
     // behind a scaling stage the block grid, whose rows belong to the slab that holds a block's LAST raw row.
@@ -87,7 +87,7 @@ struct thz_session {
 // first half of a recompute: everything up to and including the fused launch, enqueued on the context's
 // stream (tail_only: chain positions >= 6 were served from the resident spectrum)
 int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, bool *tail_only);
-// Scaling over slab edges (group_api.cpp; math_tools.rs:273-301 adds a block's s x s inputs row by row): which rows
+// Scaling over slab edges (group_session.cpp; math_tools.rs:273-301 adds a block's s x s inputs row by row): which rows
 // of the block grid slab `rank` of `world` owns when the raw grid's nx rows are cut by thz_host_slab.
 struct SlabScale {
     size_t head = 0;       // leading raw rows that complete the block the previous slab started (0: none)
