@@ -108,10 +108,12 @@ int thz_set_time_axis(thz_ctx *ctx, const float *time, size_t nt);
  * kernels for nt = 1024/2048/4096; mixed-radix "P" kernels for the lengths that
  * factor into three small radices — nt = 1001 = 7 x 11 x 13, the length of the
  * reference's real scans, and 1000 / 1200 / 1500 / 2000; half-length mixed-radix "PH" kernels for
- * 2002 / 2400 / 3000 / 4000 (twice a P length); chirp-z over the F core — "FB" kernels —
- * for the other lengths that are not a power of two; LDS Stockham "G" kernels
+ * 2002 / 2400 / 3000 / 4000 (twice a P length); chirp-z over the mixed-radix core — "FBP"
+ * kernels, convolution length 2304 / 2560 — for the other lengths in 1025 ... 1280, where a tilted
+ * 1001-sample scan lands; chirp-z over the F core — "FB" kernels —
+ * for the remaining lengths that are not a power of two; LDS Stockham "G" kernels
  * for the remaining powers of two), 1 = G kernels (Stockham / Bluestein in LDS)
- * for every length, 2 = automatic without the P kernels (A/B measurements, tests).
+ * for every length, 2 = automatic without the P, PH and FBP kernels (A/B measurements, tests).
  * Re-plans if a time axis is already set. */
 int thz_set_kernel_family(thz_ctx *ctx, int family);
 size_t thz_nt(const thz_ctx *ctx);
@@ -422,7 +424,9 @@ int thz_traffic_probe(thz_ctx *ctx, size_t npix, size_t nt, const float *d_in, f
  * UpdateType::Filter(idx) (data_thread.rs:1023) is served by re-running it from
  * the raw cube: that is the partial-recompute policy — nothing but the raw cube
  * is cached.  A non-zero tilt changes the trace length and takes the staged
- * path (tilt kernel, re-plan, transforms of the new length). */
+ * path (tilt kernel, re-plan, transforms of the new length).  A 1001-sample scan
+ * tilted onto 1025 ... 1280 samples (up to 4.8 degrees across 50 mm) then runs the
+ * fused chain as one FBP launch; beyond 1280 samples it is the FB kernels' two. */
 typedef struct thz_session thz_session;
 
 typedef struct thz_chain_cfg {

@@ -34,6 +34,7 @@ struct FBArgs {
     const cx *bf;           // M : FFT_M(b) / M
     const cx *cmask;        // nf complex multipliers on top of `mask`, or nullptr (P kernels)
     float *sum_partial;     // (gridDim.x, 2 nf): every block's sums of its traces' stored amplitudes | unwrapped phases (k_p<..., SUMS>)
+    const float *pre_win2;  // nt or nullptr: a second window behind pre_win (k_fbp<kFwd>, fft_fbp.hpp)
 };
 
 // LDS per block, in floats behind the core tables: [mask nf][pre nt][post nt], each padded to 4

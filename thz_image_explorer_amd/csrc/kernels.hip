@@ -22,6 +22,7 @@
 #include "fft_fb.hpp"
 #include "fft_p.hpp"
 #include "fft_ph.hpp"
+#include "fft_fbp.hpp"
 
 #include <cstdlib>
 
@@ -2566,6 +2567,33 @@ static void dispatch_ph(hipStream_t st, const PlanDev &P, FBArgs &A)
     }
 }
 
+// FBP kernels (fft_fbp.hpp): chirp-z over the P core at M = 2304 / 2560, one wave per pair of traces
+template <class PL, int MODE>
+static void launch_fbp(hipStream_t st, const PlanDev &P, FBArgs &A)
+{
+    A.nt = P.nt;
+    A.nf = P.nf;
+    A.w = reinterpret_cast<const cx *>(P.chirp_conj);
+    A.bf = reinterpret_cast<const cx *>(P.bfft);
+    const unsigned waves = (unsigned)FBPLayout<PL>::waves();
+    const size_t n_pairs = (A.npix + 1) / 2;
+    size_t g = (n_pairs + waves - 1) / waves;
+    if (g > (size_t)kNumCU) g = kNumCU;
+    if (g_grid_cap_override > 0 && g > (size_t)g_grid_cap_override) g = (size_t)g_grid_cap_override;
+    if (g < 1) g = 1;
+    const size_t lds = FBPLayout<PL>::lds_bytes((int)waves, P.nt);
+    PTables T{reinterpret_cast<const cx *>(P.p_t1), reinterpret_cast<const cx *>(P.p_t2)};
+    allow_dynamic_lds(k_fbp<PL, MODE>, lds);
+    THZ_LAUNCH((k_fbp<PL, MODE>), (unsigned)g, waves * kWave, lds, st, A, T);
+}
+
+template <int MODE>
+static void dispatch_fbp(hipStream_t st, const PlanDev &P, FBArgs &A)
+{
+    if (P.conv_m == FBPPlan2304::N) launch_fbp<FBPPlan2304, MODE>(st, P, A);
+    else launch_fbp<FBPPlan2560, MODE>(st, P, A);
+}
+
 // FBC: S waves per pair (fft_fb.hpp), forward and inverse as separate kernels, for the lengths
 // 1024 < nt < 8192 that are not a power of two
 
@@ -2620,6 +2648,16 @@ void launch_fft_fwd(hipStream_t st, const PlanDev &P, size_t npix, const float *
         launch_td_window(st, npix, P.nt, in, wa, data_out);
         if (wb) launch_td_window(st, npix, P.nt, data_out, wb, data_out);
         launch_fft_fwd(st, P, npix, data_out, nullptr, nullptr, nullptr, fft_out, amp_out, ph_out, mask, cmask);
+        return;
+    }
+    // FBP kernels: both windows and the windowed-trace output ride in the forward launch (no G kernel can stand in
+    // for a combination here: the plan carries no table of theirs)
+    if (P.family == kFamilyFBP) {
+        FBArgs A{};
+        A.npix = npix; A.in = in; A.pre_win = wa ? wa : wb; A.pre_win2 = wa ? wb : nullptr; A.mask = mask ? mask : P.ones;
+        A.data_out = data_out;
+        A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
+        dispatch_fbp<kFwd>(st, P, A);
         return;
     }
     // FB kernels (chirp-z lengths): same split — the windowed-trace output is its own launch
@@ -2709,6 +2747,13 @@ void launch_fft_inv(hipStream_t st, const PlanDev &P, size_t npix, const c32 *ff
         A.npix = npix; A.fft_in = reinterpret_cast<const cx *>(fft_in); A.mask = P.ones; A.post_win = win;
         A.data_out = out; A.img = img;
         dispatch_fb<kInv>(st, P, A);
+        return;
+    }
+    if (P.family == kFamilyFBP) {
+        FBArgs A{};
+        A.npix = npix; A.fft_in = reinterpret_cast<const cx *>(fft_in); A.mask = P.ones; A.post_win = win;
+        A.data_out = out; A.img = img;
+        dispatch_fbp<kInv>(st, P, A);
         return;
     }
     if ((P.family == kFamilyFB2 || P.family == kFamilyFB4 || P.family == kFamilyFB8) && P.half_n) {
@@ -2830,6 +2875,14 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
         A.post_win = post_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
         A.data_out = data_out; A.img = img;
         dispatch_fb<kPipe>(st, P, A);
+        return;
+    }
+    if (P.family == kFamilyFBP && fft_out && amp_out && ph_out && data_out) {
+        FBArgs A{};
+        A.npix = npix; A.in = raw; A.pre_win = pre_win; A.mask = mask ? mask : P.ones;
+        A.post_win = post_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
+        A.data_out = data_out; A.img = img;
+        dispatch_fbp<kPipe>(st, P, A);
         return;
     }
     if (P.big_scratch && fft_out) {  // long traces: a forward and an inverse launch around the stored spectrum

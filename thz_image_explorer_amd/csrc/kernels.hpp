@@ -41,13 +41,16 @@ struct PlanDev {
     // the split twiddles W_2N^k, k <= N / 2, behind p_t2's (even-padded) entries; the family stays the chirp-z one, whose
     // kernels serve what the PH kernels do not (a complex multiplier, thz_set_kernel_family)
     int half_n;        // N, or 0
+    // "FBP" kernels (fft_fbp.hpp): chirp-z whose convolution length conv_m = 2304 / 2560 is a P-core plan — p_t1 / p_t2
+    // are then those of length conv_m, bfft has conv_m entries, and tw / log2n describe nothing (no G kernel runs)
+    int conv_m;        // or 0
     // lengths whose transform buffers do not fit the CU's LDS (not a power of two above 8191, powers of two above
     // 16384): the G kernels with their buffers in global scratch — 2 buf_entries per wave of a grid of big_waves waves
     c32 *big_scratch;  // or nullptr
     int big_waves;
 };
 
-enum : int { kFamilyG = 0, kFamilyF = 1, kFamilyFB = 2, kFamilyFB2 = 3, kFamilyFB4 = 4, kFamilyFB8 = 5, kFamilyP = 6 };  // FB / FB2: chirp-z over the F core (fft_fb.hpp)
+enum : int { kFamilyG = 0, kFamilyF = 1, kFamilyFB = 2, kFamilyFB2 = 3, kFamilyFB4 = 4, kFamilyFB8 = 5, kFamilyP = 6, kFamilyFBP = 7 };  // FB / FB2: chirp-z over the F core (fft_fb.hpp); FBP: over the P core (fft_fbp.hpp)
 
 // one band of the batched Richardson–Lucy solve (offsets in floats into one workspace)
 struct RlBand {

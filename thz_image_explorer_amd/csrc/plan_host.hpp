@@ -21,6 +21,7 @@ struct PlanHost {
     std::vector<c32> f_t1, f_t2, f_w2n;
     std::vector<c32> p_t1, p_t2;  // P family (PH: of the half length, the split twiddles behind p_t2)
     int half_n = 0;                // PH kernels: nt = 2 half_n
+    int conv_m = 0;                // FBP kernels: convolution length (p_t1 / p_t2 / bfft are of this length)
     bool big = false;              // buffers in global scratch (k_fft_fwd_big / k_fft_inv_big)
     int big_waves = 0;             // waves of their grid = slots of the scratch
     const char *variant = "";
@@ -95,6 +96,45 @@ inline void host_fft_pow2(std::vector<std::complex<double>> &a)
     }
 }
 
+// FBP kernels (fft_fbp.hpp): convolution length and core radices for a chirp-z length, or false
+inline bool fbp_factors(size_t nt, size_t &m, int &r1, int &r2, int &r3)
+{
+    if (nt <= 1024 || nt > 1280) return false;  // 1280 < nt <= 1536 (M = 3072) stays on the F core's kernels
+    if (2 * nt - 1 <= 2304) { m = 2304; r1 = 12; r2 = 12; r3 = 16; }
+    else { m = 2560; r1 = 16; r2 = 16; r3 = 10; }
+    return true;
+}
+
+// Recursive decimation-in-time FFT in double for a length n whose prime factors are all <= 16 (the FBP convolution
+// lengths 2304 = 2^8 3^2 and 2560 = 2^9 5), table construction only: out[0 .. n) = DFT of in[0], in[stride], ...;
+// w[k] = exp(-2 pi i k / N) for the top-level length N.  O(n sum of the prime factors): a session re-plans at every
+// tilt change, so this has to stay in the class of host_fft_pow2.
+inline bool host_fft_mixed(const std::complex<double> *in, size_t n, size_t stride, std::complex<double> *out,
+                           const std::vector<std::complex<double>> &w)
+{
+    if (n == 1) {
+        out[0] = in[0];
+        return true;
+    }
+    const size_t N = w.size();
+    size_t p = 2;
+    while (n % p) ++p;
+    if (p > 16) return false;
+    const size_t m = n / p;
+    for (size_t r = 0; r < p; ++r)
+        if (!host_fft_mixed(in + r * stride, m, stride * p, out + r * m, w)) return false;
+    std::complex<double> t[16];
+    for (size_t k = 0; k < m; ++k) {
+        for (size_t r = 0; r < p; ++r) t[r] = out[r * m + k] * w[(N / n) * r * k];  // r k < n
+        for (size_t q = 0; q < p; ++q) {
+            std::complex<double> s = t[0];
+            for (size_t r = 1; r < p; ++r) s += t[r] * w[(N / p) * ((r * q) % p)];
+            out[k + m * q] = s;
+        }
+    }
+    return true;
+}
+
 // Returns false when nt is outside the supported range.
 inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p = true)
 {
@@ -109,6 +149,7 @@ inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p
     constexpr size_t kMaxTraceLength = 65536;
     if (nt > kMaxTraceLength) return false;
     P.big = false;
+    P.conv_m = 0;
     if (is_pow2(nt) && nt >= 4) {
         P.big = nt > 16384;
         P.mode = kModePow2;
@@ -122,6 +163,14 @@ inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p
         N = 1;
         while (N < 2 * nt - 1) N <<= 1;
         if (allow_f && N < 512) N = 512;  // smallest convolution length of the FB kernels (fft_fb.hpp)
+        // the lengths of a tilted 1001-sample scan: convolution on the P core at M = 2304 / 2560 instead of 4096 (a
+        // length with a plan of its own — 1200 — keeps it)
+        int f1, f2, f3;
+        size_t fm;
+        if (allow_f && allow_p && !p_factors(nt, f1, f2, f3) && fbp_factors(nt, fm, f1, f2, f3)) {
+            N = fm;
+            P.conv_m = (int)fm;
+        }
         P.variant = P.big ? "g-bluestein-stockham-global-scratch-r4r2" : "g-bluestein-stockham-lds-r4r2";
     }
     int lg = 0;
@@ -146,8 +195,9 @@ inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p
     if (wpb > 4) wpb = 4;
     P.waves_per_block = wpb;
 
-    P.tw.resize(N);
-    for (size_t m = 0; m < N; ++m) {
+    P.tw.clear();
+    if (!P.conv_m) P.tw.resize(N);  // the G / FBC kernels' W_N^m; nothing of an FBP plan reads it
+    for (size_t m = 0; m < P.tw.size(); ++m) {
         const double a = -2.0 * pi * (double)m / (double)N;
         P.tw[m] = c32{(float)std::cos(a), (float)std::sin(a)};
     }
@@ -177,7 +227,17 @@ inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p
             b[n] = chirp[n];
             b[N - n] = chirp[n];
         }
-        host_fft_pow2(b);
+        if (P.conv_m) {
+            std::vector<std::complex<double>> w(N), B(N);
+            for (size_t m = 0; m < N; ++m) {
+                const double a = -2.0 * pi * (double)m / (double)N;
+                w[m] = std::complex<double>(std::cos(a), std::sin(a));
+            }
+            if (!host_fft_mixed(b.data(), N, 1, B.data(), w)) return false;
+            b.swap(B);
+        } else {
+            host_fft_pow2(b);
+        }
         P.bfft.resize(N);
         for (size_t m = 0; m < N; ++m)
             P.bfft[m] = c32{(float)(b[m].real() / (double)N), (float)(b[m].imag() / (double)N)};
@@ -228,6 +288,26 @@ inline bool build_plan(size_t nt, PlanHost &P, bool allow_f = true, bool allow_p
         for (int k1 = 0; k1 < q1; ++k1)
             for (size_t m = 0; m < m1; ++m) {
                 const double a = -2.0 * pi * (double)((m * (size_t)k1) % nt) / (double)nt;
+                P.p_t1[(size_t)k1 * m1 + m] = c32{(float)std::cos(a), (float)std::sin(a)};
+            }
+        P.p_t2.resize(m1);
+        for (int k2 = 0; k2 < q2; ++k2)
+            for (int j3 = 0; j3 < q3; ++j3) {
+                const double a = -2.0 * pi * (double)((j3 * k2) % (int)m1) / (double)m1;
+                P.p_t2[(size_t)k2 * q3 + j3] = c32{(float)std::cos(a), (float)std::sin(a)};
+            }
+    }
+    if (P.conv_m) {
+        // FBP: the P core's tables for the convolution length M = conv_m, in the fields the P family uses
+        size_t fm;
+        fbp_factors(nt, fm, q1, q2, q3);
+        P.family = kFamilyFBP;
+        P.variant = fm == 2304 ? "fbp-bluestein-mixed-radix-12x12x16-regs-lds" : "fbp-bluestein-mixed-radix-16x16x10-regs-lds";
+        const size_t m1 = (size_t)q2 * q3;
+        P.p_t1.resize(fm);
+        for (int k1 = 0; k1 < q1; ++k1)
+            for (size_t m = 0; m < m1; ++m) {
+                const double a = -2.0 * pi * (double)((m * (size_t)k1) % fm) / (double)fm;
                 P.p_t1[(size_t)k1 * m1 + m] = c32{(float)std::cos(a), (float)std::sin(a)};
             }
         P.p_t2.resize(m1);
@@ -292,6 +372,8 @@ inline PlanDev plan_dev(const PlanHost &H, const c32 *tw, const c32 *tw_split,
         && chirp_conj && bfft)
         D.family = H.family;
     if (H.family == kFamilyP && p_t1 && p_t2 && ones) D.family = kFamilyP;
+    if (H.family == kFamilyFBP && p_t1 && p_t2 && ones && chirp_conj && bfft) D.family = kFamilyFBP;
+    D.conv_m = H.conv_m;
     D.p_t1 = p_t1;
     D.p_t2 = p_t2;
     D.half_n = (H.half_n && p_t1 && p_t2 && ones) ? H.half_n : 0;
