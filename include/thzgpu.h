@@ -242,14 +242,17 @@ int thz_pipeline(thz_ctx *ctx, size_t npix, const float *d_raw, const float *d_p
  *               ONE pass over HBM: spectrum = X * (cmask * mask), imaginary parts of bin 0 and (even
  *               nt) of the last bin forced to 0 (math_tools.rs:510-512), amplitudes = |X cmask mask|,
  *               phases those of X (band_pass_fd.rs:184-212 does not touch them either).  Fused for nt = 1024 / 2048 /
- *               4096 and 1001 / 1000 / 1200 / 1500 / 2000 (the F and P kernel families); trace lengths
- *               without a fused kernel for it run fft -> thz_apply_fd_cmask -> ifft internally.
+ *               4096, 1001 / 1000 / 1200 / 1500 / 2000 and the chirp-z lengths 1025 ... 1280 (the F, P and FBP
+ *               kernel families); trace lengths without a fused kernel for it run fft -> thz_apply_fd_cmask ->
+ *               ifft internally.
  *   d_sums      (2 nf) or NULL: sum over the npix traces of the stored amplitudes [0, nf) and of the
  *               unwrapped phases [nf, 2 nf) — the numerators of the pixel means of the ifft stage
  *               (math_tools.rs:427-440; divide by nx ny, or all-reduce the sums of the tiles first).  For
  *               nt = 1024 / 2048 / 4096 and 1001 / 1000 / 1200 / 1500 / 2000 they are taken INSIDE the launch (every block adds its
  *               traces' values to accumulators in LDS, wave by wave in a fixed order; a small pass adds the
- *               blocks' rows), for other lengths by thz_pixel_sum passes over d_amp / d_phase behind it.
+ *               blocks' rows), and so for 1025 ... 1280 (FBP kernels: every wave keeps its traces' sums in
+ *               registers and leaves one row), for other lengths by thz_pixel_sum passes over d_amp / d_phase
+ *               behind it.
  *               Deterministic; the summation order differs from the reference's sequential one (<= 2e-6
  *               relative); thz_pixel_mean is the bit-exact form.
  * d_fft, d_amp, d_phase and d_data_out are required here. */
@@ -272,6 +275,27 @@ typedef struct thz_pipeline_io {
     size_t band_lo, band_hi;
 } thz_pipeline_io;
 int thz_pipeline_ex(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io);
+
+/* thz_pipeline_ex on traces that are re-laid on the context's (extended) time axis while they are read: the Tilt
+ * Compensation's per-pixel copy (thz_tilt_apply) without the extended cube.  Sample n of pixel p is d_src[p][0] in
+ * front of the pixel's insert index, d_src[p][n - ins] * d_taper[n - ins] behind it and 0 behind the trace; io->d_raw
+ * is ignored, every output is what thz_tilt_apply + thz_pipeline_ex give, bit for bit.  With an FBP plan (the
+ * context's nt in 1025 ... 1280) this is ONE launch from the untilted cube — gather, optional complex multiplier and
+ * pixel sums included; with any other plan the traces are re-laid into scratch of the context first and the chain
+ * runs on that, so the results do not depend on the length.
+ *   d_src_sum  (nt) or NULL: sum over the npix traces of the re-laid, tapered samples (before d_pre_win) — with the
+ *              pixel count it gives the mean spectrum by linearity, mask * FFT(pre * mean trace).
+ * THZ_ERR_INVALID for nt_in == 0 or nt_in > nt.  The insert indices live on the device and are the caller's word:
+ * each in [0, nt - 1], as thz_host_tilt_plan makes them (an index outside reads no memory out of bounds, it yields
+ * the first sample or zeros). */
+typedef struct thz_tilt_src {
+    const float *d_src;            /* (npix, nt_in) untilted traces */
+    size_t nt_in;
+    const float *d_taper;          /* (nt_in) thz_host_adapted_blackman(time, 0, 7) */
+    const int32_t *d_insert_index; /* (npix), thz_host_tilt_plan */
+    float *d_src_sum;              /* (nt) or NULL */
+} thz_tilt_src;
+int thz_pipeline_tilted(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src);
 
 /* Time multiplier alone (K6): out = in * win; in place allowed. */
 int thz_apply_td_window(thz_ctx *ctx, size_t npix, const float *d_in, const float *d_win,
@@ -423,10 +447,14 @@ int thz_traffic_probe(thz_ctx *ctx, size_t npix, size_t nt, const float *d_in, f
  * the whole default chain is one HBM pass (thz_pipeline), every
  * UpdateType::Filter(idx) (data_thread.rs:1023) is served by re-running it from
  * the raw cube: that is the partial-recompute policy — nothing but the raw cube
- * is cached.  A non-zero tilt changes the trace length and takes the staged
- * path (tilt kernel, re-plan, transforms of the new length).  A 1001-sample scan
- * tilted onto 1025 ... 1280 samples (up to 4.8 degrees across 50 mm) then runs the
- * fused chain as one FBP launch; beyond 1280 samples it is the FB kernels' two. */
+ * is cached.  A non-zero tilt changes the trace length: the session re-plans for the
+ * new length.  A 1001-sample scan tilted onto 1025 ... 1280 samples (up to 4.8 degrees
+ * across 50 mm) still runs the whole chain as ONE launch from the raw cube
+ * (thz_pipeline_tilted: the re-laying is folded into the FBP kernel's loads, the
+ * complex multiplier and the pixel sums ride in the same launch); the extended cube
+ * is only built when a region of interest or a plot asks for the extended traces.
+ * Other tilted lengths take the staged path (tilt kernel into an extended cube, then
+ * the transforms of the new length; beyond 1280 samples the FB kernels' two launches). */
 typedef struct thz_session thz_session;
 
 typedef struct thz_chain_cfg {
@@ -446,8 +474,9 @@ typedef struct thz_chain_cfg {
     double td_after_low, td_after_high, td_after_width;
     /* pixel means of the ifft stage (math_tools.rs:421-440): 0 none; 1 amplitude / phase sums taken
      * inside the fused launch and avg_fft by linearity from the mean trace (<= 1e-5 of the reference's
-     * values, no extra pass over the outputs); 2 the reference's summation order bit for bit (three
-     * passes over the outputs; also what 1 falls back to for a tilted cube) */
+     * values, no extra pass over the outputs; on a tilted cube the mean trace is that of the re-laid traces:
+     * one launch's sums for the lengths 1025 ... 1280, thz_pixel_sum passes behind the launch for the others);
+     * 2 the reference's summation order bit for bit (three passes over the outputs) */
     int32_t want_means;
     /* ConfigContainer.scale_factor: the chain's first stage, math_tools::scaling
      * (math_tools.rs:242-310).  s > 1 replaces the raw cube by its s x s block

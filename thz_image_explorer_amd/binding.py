@@ -98,6 +98,11 @@ class PipelineIo(C.Structure):
                                           "d_phase", "d_data_out", "d_img", "d_sums")] + [("band_lo", C.c_size_t), ("band_hi", C.c_size_t)]
 
 
+class TiltSrc(C.Structure):
+    _fields_ = [("d_src", C.c_void_p), ("nt_in", C.c_size_t), ("d_taper", C.c_void_p), ("d_insert_index", C.c_void_p),
+                ("d_src_sum", C.c_void_p)]
+
+
 class RoiOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("signal_fft", "phase_fft", "signal", "roi_data", "count")]
 
@@ -156,6 +161,7 @@ SYMBOLS = [
     ("thz_ifft", C.c_int, [_P, _SZ, _P, _P, _P, _P]),
     ("thz_pipeline", C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("thz_pipeline_ex", C.c_int, [_P, _SZ, _P]),
+    ("thz_pipeline_tilted", C.c_int, [_P, _SZ, _P, _P]),
     ("thz_apply_td_window", C.c_int, [_P, _SZ, _P, _P, _P]),
     ("thz_intensity", C.c_int, [_P, _SZ, _P, _P]),
     ("thz_subtract_bias", C.c_int, [_P, _SZ, _P, _P]),
@@ -850,6 +856,14 @@ class Engine:
         io = PipelineIo(*[_dp(x) for x in (raw, pre_win, fd_mask, fd_cmask, post_win, fft, amp, phase, data_out, img, sums)],
                         *(band if band else (0, 0)))
         self._check(self.lib.thz_pipeline_ex(self.ctx, npix, C.byref(io)))
+
+    def pipeline_tilted(self, npix, src, nt_in, taper, insert_index, pre_win, fd_mask, fd_cmask, post_win, fft, amp, phase,
+                        data_out, img=None, sums=None, src_sum=None):
+        """thz_pipeline_tilted: pipeline_ex on (npix, nt_in) traces that are re-laid on the context's extended axis while
+        they are read (taper, insert_index as for tilt_apply); src_sum: (nt) sums of the re-laid, tapered samples"""
+        io = PipelineIo(*[_dp(x) for x in (None, pre_win, fd_mask, fd_cmask, post_win, fft, amp, phase, data_out, img, sums)], 0, 0)
+        ts = TiltSrc(_dp(src), nt_in, _dp(taper), _dp(insert_index), _dp(src_sum))
+        self._check(self.lib.thz_pipeline_tilted(self.ctx, npix, C.byref(io), C.byref(ts)))
 
     def pipeline(self, npix, raw, pre_win, fd_mask, post_win, fft, amp, phase, data_out, img):
         self._check(self.lib.thz_pipeline(self.ctx, npix, _dp(raw), _dp(pre_win), _dp(fd_mask),

@@ -51,6 +51,7 @@ void thz_destroy(thz_ctx *ctx)
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
     if (ctx->d_big) (void)hipFree(ctx->d_big);
     if (ctx->ws) (void)hipFree(ctx->ws);
+    if (ctx->tilt_scratch) (void)hipFree(ctx->tilt_scratch);
     for (auto &g : ctx->dc_graph) g.drop();
     ctx->drop_dc_tables();
     for (auto &b : ctx->dc_pool) (void)hipFree(b.p);
@@ -78,6 +79,9 @@ int thz_release_scratch(thz_ctx *ctx)
     if (ctx->ws) (void)hipFree(ctx->ws);
     ctx->ws = nullptr;
     ctx->ws_bytes = 0;
+    if (ctx->tilt_scratch) (void)hipFree(ctx->tilt_scratch);
+    ctx->tilt_scratch = nullptr;
+    ctx->tilt_scratch_floats = 0;
     return THZ_OK;
 }
 
@@ -505,7 +509,78 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
     return thz_pixel_sum(ctx, npix, nf, 1, io->d_phase, io->d_sums + nf);
 }
 
+// thz_pipeline_tilted with the real multiplier's non-zero range known (the session), as pipeline_ex_band
+int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src, size_t band_lo,
+                         size_t band_hi)
+{
+    if (int rc = need_plan(ctx)) return rc;
+    if (!io || !io->d_data_out || !io->d_fft || !io->d_amp || !io->d_phase)
+        return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: d_fft, d_amp, d_phase and d_data_out are required");
+    if (!src || !src->d_src || !src->d_taper || !src->d_insert_index)
+        return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: d_src, d_taper and d_insert_index are required");
+    const size_t nt = (size_t)ctx->plan_d.nt, nf = (size_t)ctx->plan_d.nf;
+    if (src->nt_in == 0 || src->nt_in > nt)
+        return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: nt_in must be in [1, nt] (the traces are re-laid on the context's axis)");
+    if (npix == 0) {
+        if (io->d_sums) HIP_TRY(ctx, hipMemsetAsync(io->d_sums, 0, 2 * nf * sizeof(float), ctx->stream));
+        if (src->d_src_sum) HIP_TRY(ctx, hipMemsetAsync(src->d_src_sum, 0, nt * sizeof(float), ctx->stream));
+        return THZ_OK;
+    }
+    const FBPTilt TL{src->d_src, src->d_taper, src->d_insert_index, (int)src->nt_in};
+    if (ctx->plan_d.family == kFamilyFBP) {
+        // ONE launch from the untilted cube: gather, multiplier and the wave rows of the sums (fft_fbp.hpp); the
+        // re-laid traces' own sum is a small gather pass over the untilted cube (4 nt_in bytes per trace).
+        // THZ_NO_FUSED_SUMS: developer knob as in thz_pipeline_ex, the sums as second passes for A/B measurements
+        const size_t sum_rows = (io->d_sums && !getenv("THZ_NO_FUSED_SUMS")) ? pipeline_sum_rows(ctx->plan_d, npix, io->d_fd_cmask != nullptr) : 0;
+        const size_t src_rows = src->d_src_sum ? tilt_sum_rows(npix) : 0;
+        if (sum_rows || src_rows)
+            if (int rc = ensure_ws(ctx, (sum_rows * 2 * nf + src_rows * nt) * sizeof(float))) return rc;
+        float *d_partial = sum_rows ? reinterpret_cast<float *>(ctx->ws) : nullptr;
+        {
+            StageTimer t(ctx, THZ_STAGE_PIPELINE);
+            launch_pipeline_tilted(ctx->stream, ctx->plan_d, npix, TL, io->d_pre_win, io->d_fd_mask, io->d_post_win,
+                                   reinterpret_cast<c32 *>(io->d_fft), io->d_amp, io->d_phase, io->d_data_out, io->d_img,
+                                   reinterpret_cast<const c32 *>(io->d_fd_cmask), d_partial);
+            if (int rc = check_launch(ctx)) return rc;
+        }
+        if (io->d_sums || src->d_src_sum) {
+            StageTimer t(ctx, THZ_STAGE_MEAN);
+            if (d_partial) launch_sum_rows_f64(ctx->stream, d_partial, sum_rows, 2 * nf, io->d_sums);
+            if (src->d_src_sum)
+                launch_tilt_sum(ctx->stream, npix, (int)nt, TL, reinterpret_cast<float *>(ctx->ws) + sum_rows * 2 * nf, src->d_src_sum);
+            if (int rc = check_launch(ctx)) return rc;
+        }
+        if (io->d_sums && !d_partial) {
+            if (int rc = thz_pixel_sum(ctx, npix, nf, 1, io->d_amp, io->d_sums)) return rc;
+            return thz_pixel_sum(ctx, npix, nf, 1, io->d_phase, io->d_sums + nf);
+        }
+        return THZ_OK;
+    }
+    // every other plan: the staged form — the re-laid traces into scratch of the context, the chain on them
+    if (ctx->tilt_scratch_floats < npix * nt) {
+        if (ctx->tilt_scratch) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipFree(ctx->tilt_scratch));
+            ctx->tilt_scratch = nullptr;
+            ctx->tilt_scratch_floats = 0;
+        }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->tilt_scratch, npix * nt * sizeof(float)));
+        ctx->tilt_scratch_floats = npix * nt;
+    }
+    if (int rc = thz_tilt_apply(ctx, npix, src->d_src, src->nt_in, src->d_taper, src->d_insert_index, nt, ctx->tilt_scratch)) return rc;
+    thz_pipeline_io staged = *io;
+    staged.d_raw = ctx->tilt_scratch;
+    if (int rc = pipeline_ex_band(ctx, npix, &staged, band_lo, band_hi)) return rc;
+    if (src->d_src_sum) return thz_pixel_sum(ctx, npix, nt, 1, ctx->tilt_scratch, src->d_src_sum);
+    return THZ_OK;
+}
+
 extern "C" {
+
+int thz_pipeline_tilted(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src)
+{
+    return pipeline_tilted_band(ctx, npix, io, src, io ? io->band_lo : 0, io ? io->band_hi : 0);
+}
 
 int thz_apply_td_window(thz_ctx *ctx, size_t npix, const float *d_in, const float *d_win,
                         float *d_out)

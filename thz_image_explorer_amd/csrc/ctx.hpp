@@ -29,6 +29,8 @@ struct thz_ctx {
     hipStream_t aux_streams[3] = {nullptr, nullptr, nullptr};  // the deconvolution's extra chains (created on first use)
     void *ws = nullptr;  // scratch workspace (pixel means, ROI lists)
     size_t ws_bytes = 0;
+    float *tilt_scratch = nullptr;  // thz_pipeline_tilted on a plan without the gather: the re-laid traces
+    size_t tilt_scratch_floats = 0;
     // device blocks of the last thz_deconvolve call, kept for the next one: a call of the same geometry then neither
     // allocates nor frees (eleven hipMalloc + hipFree pairs measured 0.8 ms of a 10 ms call); blocks a call did
     // not use are freed at its end, so a change of geometry does not accumulate memory
@@ -223,6 +225,9 @@ using namespace thz_api;
 
 // api.cpp: thz_pipeline_ex with the real multiplier's non-zero range [band_lo, band_hi) known (0, 0: unknown)
 int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi);
+// api.cpp: thz_pipeline_tilted likewise
+int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src, size_t band_lo,
+                         size_t band_hi);
 // api.cpp: order-free column sums over all rows (d_list null) or over the listed rows of d_arr
 int pixel_sum_rows(thz_ctx *ctx, const float *d_arr, const uint32_t *d_list, size_t npix, size_t L, float *d_out);
 

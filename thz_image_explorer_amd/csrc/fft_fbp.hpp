@@ -25,8 +25,20 @@
 //
 // LDS per block: [T1: M cx][T2: R2 R3 cx][per wave: M cx][mask nf][pre nt][post nt] — 31.5 KB + 18.0 KB per wave at
 // M = 2304 (7 waves in 160 KB), 34.5 KB + 20.0 KB at M = 2560 (6 waves); the block is sized for the longest trace of
-// its M.  No complex multiplier and no in-launch sums here: those requests take the entry points' second passes
-// (launch_fd_cmask, thz_pixel_sum).
+// its M.
+//
+// Three compile-time extras of the fused chain (k_fbp<P, kPipe, TILT, CM, SUMS>; the plain chain and the stage forms
+// are the instantiations without them and carry none of their code):
+//   TILT  the Tilt Compensation folded into the forward loads (FBPTilt): sample n of pixel p is what k_tilt would have
+//         written to the extended cube — src[p][0] in front of the insert index, src[p][n - ins] taper[n - ins] behind
+//         it, 0 behind the trace — one f32 multiply in front of the window's, so every output is the staged path's bit
+//         for bit.  The taper is read from memory (cache-resident: 4 KB for the whole launch); LDS has no room for it.
+//   CM    nf complex multipliers on top of the real mask, as k_p's: [mask nf] becomes [m H: nf cx] (2 320 / 2 576 B
+//         more, still 7 / 6 waves), stored spectrum X (m H), amplitude |X m H|, phases of X, real bins' Im +0.
+//   SUMS  the launch's sums of the stored amplitudes and unwrapped phases.  A lane owns bins 256 g + 4 lane + c of the
+//         three epilogue groups, so a wave keeps 24 accumulators in registers over all of its trips and stores ONE row
+//         of A.sum_partial at the end (grid x waves rows of 2 nf floats, every entry written): no LDS, no tickets, no
+//         barrier, and the order of every bin's additions is fixed.
 #pragma once
 
 #include "fft_fb.hpp"
@@ -42,10 +54,10 @@ struct FBPLayout {
     static constexpr int M = P::N;
     static constexpr int kMaxNt = M / 2;  // 2 nt - 1 <= M
     static constexpr int pad4(int v) { return (v + 3) & ~3; }
-    static constexpr size_t lds_bytes(int waves, int nt)
+    static constexpr size_t lds_bytes(int waves, int nt, bool cm = false)
     {
         return (size_t)(P::T1_ENTRIES + P::T2_ENTRIES + waves * P::WAVE_ENTRIES) * sizeof(cx)
-               + (size_t)(pad4(nt / 2 + 1) + 2 * pad4(nt)) * sizeof(float);
+               + (size_t)((cm ? 2 : 1) * pad4(nt / 2 + 1) + 2 * pad4(nt)) * sizeof(float);
     }
     // waves of a block: as many as LDS holds next to the tables at the longest trace of this M
     static constexpr int waves()
@@ -54,6 +66,7 @@ struct FBPLayout {
         while (w > 1 && lds_bytes(w, kMaxNt) > (size_t)160 * 1024) --w;
         return w;
     }
+    static constexpr int kGroups = 3;  // epilogue groups of 256 bins: 513 <= nf <= 641 for every length of these plans
 };
 
 template <int R, int J>
@@ -115,9 +128,12 @@ __device__ __forceinline__ void fbp_multiply_transform(cx *buf, const cx *__rest
 
 // A.pre_win2 (forward only): a second window behind pre_win, applied as its own f32 multiply; A.data_out (forward
 // only): the windowed traces, the stage's `data` output.
-template <class P, int MODE>
-__global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A, PTables T)
+template <class P, int MODE, bool TILT = false, bool CM = false, bool SUMS = false>
+__global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A, PTables T, FBPTilt TL)
 {
+    static_assert(MODE == kPipe || !(TILT || CM || SUMS), "tilt gather, complex multiplier and sums: the fused chain");
+    static_assert(FBPLayout<P>::lds_bytes(FBPLayout<P>::waves(), FBPLayout<P>::kMaxNt, true) <= (size_t)160 * 1024,
+                  "the multiplier table fits next to the plain chain's waves");
     THZ_DYN_LDS(lds);
     constexpr int R1 = P::R1, H1 = R1 / 2, M1 = P::M1, WE = P::WAVE_ENTRIES;
     constexpr int RD1 = PAddr<P, 1>::RD1;
@@ -130,11 +146,20 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
     cx *t2 = t1 + P::T1_ENTRIES;
     cx *buf = t2 + P::T2_ENTRIES + (size_t)wib * WE;
     float *mask_s = reinterpret_cast<float *>(t2 + P::T2_ENTRIES + (size_t)wpb * WE);
-    float *pre_s = mask_s + LY::pad4(nf);
+    float *pre_s = mask_s + (CM ? 2 : 1) * LY::pad4(nf);
     float *post_s = pre_s + LY::pad4(L);  // the forward kernel keeps its second window here
     for (int i = (int)threadIdx.x; i < P::T1_ENTRIES; i += (int)blockDim.x) t1[i] = T.t1[i];
     for (int i = (int)threadIdx.x; i < M1; i += (int)blockDim.x) t2[i] = T.t2[i];
-    for (int i = (int)threadIdx.x; i < nf; i += (int)blockDim.x) mask_s[i] = A.mask[i];
+    if constexpr (CM) {
+        cx *cm = reinterpret_cast<cx *>(mask_s);
+        for (int i = (int)threadIdx.x; i < nf; i += (int)blockDim.x) {
+            const float m = A.mask[i];
+            const cx h = A.cmask[i];
+            cm[i] = cx{h.x * m, h.y * m};
+        }
+    } else {
+        for (int i = (int)threadIdx.x; i < nf; i += (int)blockDim.x) mask_s[i] = A.mask[i];
+    }
     for (int i = (int)threadIdx.x; i < L; i += (int)blockDim.x) {
         pre_s[i] = A.pre_win ? A.pre_win[i] : 1.0f;
         if constexpr (MODE == kFwd) post_s[i] = A.pre_win2 ? A.pre_win2[i] : 1.0f;
@@ -151,6 +176,15 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
     const int y2_base = (L + 4) & ~3;          // Y2[k] lives at y2_base + k: behind everything F uses (< 3 nt / 2 + 4 < M)
     const size_t n_pairs = (A.npix + 1) / 2;
     const size_t stride = (size_t)gridDim.x * wpb;
+    // SUMS: this wave's sums over all of its trips, [group][bin of the lane's quad]: amplitudes | unwrapped phases
+    constexpr int NG = LY::kGroups;
+    float sum_a[NG][4], sum_p[NG][4];
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sum_a[g][c] = sum_p[g][c] = 0.0f;
+    }
 
     for (size_t q = (size_t)blockIdx.x * wpb + wib; q < n_pairs; q += stride) {
         const size_t p = 2 * q;
@@ -171,18 +205,59 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
             // indices are clamped and the value selected, every load of the pair is issued before the first use.
             // The windowed samples come first and each trace's largest |value| is taken (PairScale); the chirp multiply
             // follows once both scales are known.
-            const float *x1 = A.in + p * (size_t)L;
-            const float *x2 = has2 ? x1 + L : x1;
+            const size_t row = TILT ? (size_t)TL.nt_in : (size_t)L;
+            const float *x1 = (TILT ? TL.src : A.in) + p * row;
+            const float *x2 = has2 ? x1 + row : x1;
             float xa[RD1][H1], xb[RD1][H1];
+            if constexpr (TILT) {
+                // the extended trace as k_tilt lays it out, gathered: index clamped into the source trace, value
+                // selected — in front of the insert index the trace's first sample (untapered), behind the trace zero.
+                // The two traces of a pair have their own insert indices (wave-uniform).  Every sample load of the pair
+                // is issued first, as in the plain chain; the taper (cache-resident) follows round by round
+                const int NI = TL.nt_in;
+                const int in1 = THZ_UNIFORM(TL.ins[p]), in2 = THZ_UNIFORM(TL.ins[has2 ? p + 1 : p]);
+                const float *tp = launder_uniform(TL.taper);
 #pragma unroll
-            for (int i = 0; i < RD1; ++i)
+                for (int i = 0; i < RD1; ++i)
 #pragma unroll
-                for (int j = 0; j < H1; ++j) {
-                    const int n = M1 * j + ad.m1[i];
-                    const unsigned nn = (unsigned)(n < L ? n : L - 1);
-                    xa[i][j] = ld_off(x1, nn);
-                    xb[i][j] = ld_off(x2, nn);
+                    for (int j = 0; j < H1; ++j) {
+                        const int n = M1 * j + ad.m1[i];
+                        const int nn = n < L ? n : L - 1;
+                        const int j1 = nn - in1, j2 = nn - in2;
+                        xa[i][j] = ld_off(x1, (unsigned)(j1 < 0 ? 0 : (j1 < NI ? j1 : NI - 1)));
+                        xb[i][j] = ld_off(x2, (unsigned)(j2 < 0 ? 0 : (j2 < NI ? j2 : NI - 1)));
+                    }
+#pragma unroll
+                for (int i = 0; i < RD1; ++i) {
+                    float ta[H1], tb[H1];
+#pragma unroll
+                    for (int j = 0; j < H1; ++j) {
+                        const int n = M1 * j + ad.m1[i];
+                        const int nn = n < L ? n : L - 1;
+                        const int j1 = nn - in1, j2 = nn - in2;
+                        ta[j] = ld_off(tp, (unsigned)(j1 < 0 ? 0 : (j1 < NI ? j1 : NI - 1)));
+                        tb[j] = ld_off(tp, (unsigned)(j2 < 0 ? 0 : (j2 < NI ? j2 : NI - 1)));
+                    }
+#pragma unroll
+                    for (int j = 0; j < H1; ++j) {
+                        const int n = M1 * j + ad.m1[i];
+                        const int nn = n < L ? n : L - 1;
+                        const int j1 = nn - in1, j2 = nn - in2;
+                        xa[i][j] = j1 < 0 ? xa[i][j] : (j1 < NI ? xa[i][j] * ta[j] : 0.0f);
+                        xb[i][j] = j2 < 0 ? xb[i][j] : (j2 < NI ? xb[i][j] * tb[j] : 0.0f);
+                    }
                 }
+            } else {
+#pragma unroll
+                for (int i = 0; i < RD1; ++i)
+#pragma unroll
+                    for (int j = 0; j < H1; ++j) {
+                        const int n = M1 * j + ad.m1[i];
+                        const unsigned nn = (unsigned)(n < L ? n : L - 1);
+                        xa[i][j] = ld_off(x1, nn);
+                        xb[i][j] = ld_off(x2, nn);
+                    }
+            }
             unsigned ma = 0u, mb = 0u;
 #pragma unroll
             for (int i = 0; i < RD1; ++i) {
@@ -236,12 +311,17 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
             {
                 const float h1 = 0.5f * e1.out, h2 = 0.5f * e2.out;
                 FBUnwrap u1, u2;
-#pragma unroll 1
-                for (int g = 0; g < n_groups; ++g) {
+                // SUMS: the groups unrolled, so that the accumulators of a group are registers of their own
+                const int g_end = SUMS ? NG : n_groups;
+                constexpr int kUnrollGroups = SUMS ? NG : 1;
+#pragma unroll kUnrollGroups
+                for (int g = 0; g < g_end; ++g) {
+                    if constexpr (SUMS)
+                        if (g >= n_groups) continue;  // (uniform; never for the lengths of these plans)
                     const int k0 = 256 * g + lb4;
-                    cx X1[4], X2[4];
+                    cx X1[4], X2[4], h[4];
                     float m[4];
-                    bool ok[4];
+                    bool ok[4], rb[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int k = k0 + c;
@@ -259,19 +339,45 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
                         X1[c] = cx{h1 * (Fk.x + Fm.x), h1 * (Fk.y - Fm.y)};
                         // (Fk - conj Fm) / 2i = (-i/2) (dx + i dy) = (dy/2, -dx/2)
                         X2[c] = cx{h2 * (Fk.y + Fm.y), -h2 * (Fk.x - Fm.x)};
-                        m[c] = mask_l[kc];
+                        if constexpr (CM) h[c] = reinterpret_cast<const cx *>(mask_l)[kc];
+                        else m[c] = mask_l[kc];
                         // real input: DC / Nyquist bins are real, with a POSITIVE zero as imaginary part; a zero trace's
                         // spectrum is +0.0 — both on the bit pattern (p_zero_if)
                         const bool real_bin = k == 0 || ((L & 1) == 0 && k == nf - 1);
                         X1[c] = cx{p_zero_if(X1[c].x, e1.zero), p_zero_if(X1[c].y, real_bin || e1.zero)};
                         X2[c] = cx{p_zero_if(X2[c].x, e2.zero), p_zero_if(X2[c].y, real_bin || e2.zero)};
+                        rb[c] = real_bin;
                     }
                     const size_t o1 = p * (size_t)nf + k0;
-                    fb_finish_bins(X1, m, ok, g, lane, u1, A.fft_out ? A.fft_out + o1 : nullptr,
-                                   A.amp_out ? A.amp_out + o1 : nullptr, A.ph_out ? A.ph_out + o1 : nullptr);
-                    if (has2)
-                        fb_finish_bins(X2, m, ok, g, lane, u2, A.fft_out ? A.fft_out + o1 + nf : nullptr,
-                                       A.amp_out ? A.amp_out + o1 + nf : nullptr, A.ph_out ? A.ph_out + o1 + nf : nullptr);
+                    cx Y1[4], Y2[4];  // the multiplied spectra (CM)
+                    if constexpr (CM) {
+                        fb_finish_bins_c(X1, h, rb, ok, g, lane, u1, A.fft_out ? A.fft_out + o1 : nullptr,
+                                         A.amp_out ? A.amp_out + o1 : nullptr, A.ph_out ? A.ph_out + o1 : nullptr, Y1);
+                        if (has2)
+                            fb_finish_bins_c(X2, h, rb, ok, g, lane, u2, A.fft_out ? A.fft_out + o1 + nf : nullptr,
+                                             A.amp_out ? A.amp_out + o1 + nf : nullptr, A.ph_out ? A.ph_out + o1 + nf : nullptr, Y2);
+                    } else {
+                        fb_finish_bins(X1, m, ok, g, lane, u1, A.fft_out ? A.fft_out + o1 : nullptr,
+                                       A.amp_out ? A.amp_out + o1 : nullptr, A.ph_out ? A.ph_out + o1 : nullptr);
+                        if (has2)
+                            fb_finish_bins(X2, m, ok, g, lane, u2, A.fft_out ? A.fft_out + o1 + nf : nullptr,
+                                           A.amp_out ? A.amp_out + o1 + nf : nullptr, A.ph_out ? A.ph_out + o1 + nf : nullptr);
+                    }
+                    if constexpr (SUMS) {
+                        // first trace, then second: u.a / u.y are 0 where the bin does not exist
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            sum_a[g][c] += u1.a[c];
+                            sum_p[g][c] += u1.y[c];
+                        }
+                        if (has2) {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                sum_a[g][c] += u2.a[c];
+                                sum_p[g][c] += u2.y[c];
+                            }
+                        }
+                    }
                     // masked spectra for the inverse: Y1[k] over c[k] — only its owner reads slot k or nt-k — and
                     // Y2[k] behind everything F uses.  The products are the stored ones (rounded before anything is
                     // added to them: they pass through LDS), so that the inverse transforms exactly the spectrum that
@@ -280,9 +386,9 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
                             if (ok[c]) {
-                                const cx y1 = cx{X1[c].x * m[c], X1[c].y * m[c]};
+                                const cx y1 = CM ? Y1[c] : cx{X1[c].x * m[c], X1[c].y * m[c]};
                                 // a missing second trace is exactly zero, as in the stand-alone inverse
-                                const cx y2 = has2 ? cx{X2[c].x * m[c], X2[c].y * m[c]} : cx{0.0f, 0.0f};
+                                const cx y2 = !has2 ? cx{0.0f, 0.0f} : CM ? Y2[c] : cx{X2[c].x * m[c], X2[c].y * m[c]};
                                 ym1 = umax(ym1, umax(abs_bits(y1.x), abs_bits(y1.y)));
                                 ym2 = umax(ym2, umax(abs_bits(y2.x), abs_bits(y2.y)));
                                 buf[k0 + c] = y1;
@@ -387,6 +493,20 @@ __global__ __launch_bounds__(FBPLayout<P>::waves() * kWave) void k_fbp(FBArgs A,
             }
         }
         wave_sync();
+    }
+    if constexpr (SUMS) {
+        // one row per wave, every entry written (a wave without a pair writes zeros)
+        float *row = A.sum_partial + ((size_t)blockIdx.x * wpb + wib) * (size_t)(2 * nf);
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int k = 256 * g + 4 * lane + c;
+                if (k < nf) {
+                    row[k] = sum_a[g][c];
+                    row[nf + k] = sum_p[g][c];
+                }
+            }
     }
 }
 

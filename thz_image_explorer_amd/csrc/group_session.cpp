@@ -99,8 +99,8 @@ static int group_means(thz_group_session *gs, const thz_chain_cfg *cfg, bool sin
     std::vector<float *> bufs;
     // amplitude / phase sums of the fused launch (2 nf), or — a tilted cube — spectrum, amplitude and phase sums
     // (4 nf).  The sum of the SOURCE traces in front of them (avg_fft follows from it by linearity) was all-reduced
-    // at upload for the raw cube; a block-averaged source's is the slab's own and goes along.
-    const bool src_too = s0->msum_fast && s0->d_src != s0->d_raw;
+    // at upload for the raw cube; a block-averaged or re-laid (tilted) source's is the slab's own and goes along.
+    const bool src_too = s0->src_sum_own;
     for (thz_session *s : gs->sess) bufs.push_back(src_too ? s->d_msum : s->d_msum + nt_out);
     const size_t count = (s0->msum_passes ? 4 * nf : 2 * nf) + (src_too ? nt_out : 0);
     if (int rc = thz_group_all_reduce_sum(g, bufs.data(), count)) return rc;

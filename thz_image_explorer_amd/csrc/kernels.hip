@@ -893,6 +893,47 @@ __global__ __launch_bounds__(256) void k_tilt(size_t npix, int nt_in, int nt_out
     }
 }
 
+// Column sums of the cube k_tilt would write, without writing it: block b adds the re-laid samples of pixels
+// b, b + G, ... (thread t owns samples t, t + 256, ...: KC chunks cover the trace; two pixels' loads in flight) into
+// row b of `partial`; every entry of every row is written.
+template <int KC>
+__global__ __launch_bounds__(256) void k_tilt_sum(size_t npix, int nt_in, int nt_out, const float *__restrict__ in,
+                                                  const float *__restrict__ taper, const int *__restrict__ insert_index,
+                                                  float *__restrict__ partial)
+{
+    float acc[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) acc[k] = 0.0f;
+    const size_t G = gridDim.x;
+    for (size_t p0 = blockIdx.x; p0 < npix; p0 += 2 * G) {
+        const size_t p1 = p0 + G < npix ? p0 + G : p0;  // (the second pixel of the last trip may not exist)
+        const bool two = p0 + G < npix;
+        const int ins0 = insert_index[p0], ins1 = insert_index[p1];
+        const float *r0 = in + p0 * (size_t)nt_in, *r1 = in + p1 * (size_t)nt_in;
+        float v0[KC], v1[KC], t0[KC], t1[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const int e = (int)threadIdx.x + 256 * k;
+            const int j0 = e - ins0, j1 = e - ins1;
+            const int c0 = j0 < 0 ? 0 : (j0 < nt_in ? j0 : nt_in - 1), c1 = j1 < 0 ? 0 : (j1 < nt_in ? j1 : nt_in - 1);
+            v0[k] = r0[c0]; t0[k] = taper[c0];
+            v1[k] = r1[c1]; t1[k] = taper[c1];
+        }
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const int e = (int)threadIdx.x + 256 * k;
+            const int j0 = e - ins0, j1 = e - ins1;
+            acc[k] += j0 < 0 ? v0[k] : (j0 < nt_in ? v0[k] * t0[k] : 0.0f);
+            if (two) acc[k] += j1 < 0 ? v1[k] : (j1 < nt_in ? v1[k] * t1[k] : 0.0f);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const int e = (int)threadIdx.x + 256 * k;
+        if (e < nt_out) partial[(size_t)blockIdx.x * nt_out + e] = acc[k];
+    }
+}
+
 // Block mean over s x s pixels (math_tools.rs:273-301): one wave per output pixel, sample axis
 // across the lanes, the s*s inputs added in the reference's i-outer / j-inner order.
 // VEC: rows are whole 16-byte chunks at 16-byte-aligned addresses — four samples per lane and access.
@@ -2568,23 +2609,31 @@ static void dispatch_ph(hipStream_t st, const PlanDev &P, FBArgs &A)
 }
 
 // FBP kernels (fft_fbp.hpp): chirp-z over the P core at M = 2304 / 2560, one wave per pair of traces
-template <class PL, int MODE>
-static void launch_fbp(hipStream_t st, const PlanDev &P, FBArgs &A)
+template <class PL>
+static size_t fbp_grid(size_t npix)
+{
+    const unsigned waves = (unsigned)FBPLayout<PL>::waves();
+    const size_t n_pairs = (npix + 1) / 2;
+    size_t g = (n_pairs + waves - 1) / waves;
+    if (g > (size_t)kNumCU) g = kNumCU;
+    if (g_grid_cap_override > 0 && g > (size_t)g_grid_cap_override) g = (size_t)g_grid_cap_override;
+    if (g < 1) g = 1;
+    return g;
+}
+
+template <class PL, int MODE, bool TILT = false, bool CM = false, bool SUMS = false>
+static void launch_fbp(hipStream_t st, const PlanDev &P, FBArgs &A, const FBPTilt &TL = FBPTilt{})
 {
     A.nt = P.nt;
     A.nf = P.nf;
     A.w = reinterpret_cast<const cx *>(P.chirp_conj);
     A.bf = reinterpret_cast<const cx *>(P.bfft);
     const unsigned waves = (unsigned)FBPLayout<PL>::waves();
-    const size_t n_pairs = (A.npix + 1) / 2;
-    size_t g = (n_pairs + waves - 1) / waves;
-    if (g > (size_t)kNumCU) g = kNumCU;
-    if (g_grid_cap_override > 0 && g > (size_t)g_grid_cap_override) g = (size_t)g_grid_cap_override;
-    if (g < 1) g = 1;
-    const size_t lds = FBPLayout<PL>::lds_bytes((int)waves, P.nt);
+    const size_t g = fbp_grid<PL>(A.npix);
+    const size_t lds = FBPLayout<PL>::lds_bytes((int)waves, P.nt, CM);
     PTables T{reinterpret_cast<const cx *>(P.p_t1), reinterpret_cast<const cx *>(P.p_t2)};
-    allow_dynamic_lds(k_fbp<PL, MODE>, lds);
-    THZ_LAUNCH((k_fbp<PL, MODE>), (unsigned)g, waves * kWave, lds, st, A, T);
+    allow_dynamic_lds(k_fbp<PL, MODE, TILT, CM, SUMS>, lds);
+    THZ_LAUNCH((k_fbp<PL, MODE, TILT, CM, SUMS>), (unsigned)g, waves * kWave, lds, st, A, T, TL);
 }
 
 template <int MODE>
@@ -2592,6 +2641,31 @@ static void dispatch_fbp(hipStream_t st, const PlanDev &P, FBArgs &A)
 {
     if (P.conv_m == FBPPlan2304::N) launch_fbp<FBPPlan2304, MODE>(st, P, A);
     else launch_fbp<FBPPlan2560, MODE>(st, P, A);
+}
+
+// the fused chain with its compile-time extras: A.cmask -> CM, A.sum_partial -> SUMS, TL (or null) -> TILT
+template <class PL, bool TILT>
+static void launch_fbp_pipe(hipStream_t st, const PlanDev &P, FBArgs &A, const FBPTilt &TL)
+{
+    const int sel = (A.cmask ? 1 : 0) | (A.sum_partial ? 2 : 0);
+    switch (sel) {
+    case 3: launch_fbp<PL, kPipe, TILT, true, true>(st, P, A, TL); break;
+    case 2: launch_fbp<PL, kPipe, TILT, false, true>(st, P, A, TL); break;
+    case 1: launch_fbp<PL, kPipe, TILT, true, false>(st, P, A, TL); break;
+    default: launch_fbp<PL, kPipe, TILT, false, false>(st, P, A, TL); break;
+    }
+}
+
+static void dispatch_fbp_pipe(hipStream_t st, const PlanDev &P, FBArgs &A, const FBPTilt *TL)
+{
+    const bool small = P.conv_m == FBPPlan2304::N;
+    if (TL) {
+        if (small) launch_fbp_pipe<FBPPlan2304, true>(st, P, A, *TL);
+        else launch_fbp_pipe<FBPPlan2560, true>(st, P, A, *TL);
+    } else {
+        if (small) launch_fbp_pipe<FBPPlan2304, false>(st, P, A, FBPTilt{});
+        else launch_fbp_pipe<FBPPlan2560, false>(st, P, A, FBPTilt{});
+    }
 }
 
 // FBC: S waves per pair (fft_fb.hpp), forward and inverse as separate kernels, for the lengths
@@ -2813,6 +2887,10 @@ size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4
         default: return p_sum_rows<PPlan1000>(npix, cmask);
         }
     }
+    if (P.family == kFamilyFBP) {  // one row per wave of the grid (fft_fbp.hpp, SUMS), with or without a multiplier
+        if (P.conv_m == FBPPlan2304::N) return fbp_grid<FBPPlan2304>(npix) * (size_t)FBPLayout<FBPPlan2304>::waves();
+        return fbp_grid<FBPPlan2560>(npix) * (size_t)FBPLayout<FBPPlan2560>::waves();
+    }
     if (P.family != kFamilyF) return 0;
     switch (P.nt) {
     case 4096: return f_sum_rows<FPlan4096>(npix, cmask, cmask && f_band_fits(P, band_lo4, band_n));
@@ -2837,7 +2915,7 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
         dispatch_f<kPipe>(st, P, A, true);
         return;
     }
-    if (cmask && !(P.family == kFamilyP && fft_out && amp_out && ph_out && data_out)) {
+    if (cmask && !((P.family == kFamilyP || P.family == kFamilyFBP) && fft_out && amp_out && ph_out && data_out)) {
         // every other family: the complex multiply is its own pass over the stored spectrum
         launch_fft_fwd(st, P, npix, raw, pre_win, nullptr, nullptr, fft_out, amp_out, ph_out, mask, cmask);
         launch_fft_inv(st, P, npix, fft_out, post_win, data_out, img);
@@ -2882,7 +2960,9 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
         A.npix = npix; A.in = raw; A.pre_win = pre_win; A.mask = mask ? mask : P.ones;
         A.post_win = post_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
         A.data_out = data_out; A.img = img;
-        dispatch_fbp<kPipe>(st, P, A);
+        A.cmask = reinterpret_cast<const cx *>(cmask);
+        A.sum_partial = sum_partial;  // pipeline_sum_rows(P, npix, cmask) rows, or null
+        dispatch_fbp_pipe(st, P, A, nullptr);
         return;
     }
     if (P.big_scratch && fft_out) {  // long traces: a forward and an inverse launch around the stored spectrum
@@ -2903,6 +2983,38 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
     allow_dynamic_lds(k_pipeline, lds);
     THZ_LAUNCH(k_pipeline, grid, block, lds, st, P, npix, raw, pre_win, mask, post_win, fft_out,
                amp_out, ph_out, data_out, img);
+}
+
+bool launch_pipeline_tilted(hipStream_t st, const PlanDev &P, size_t npix, const FBPTilt &tilt, const float *pre_win,
+                            const float *mask, const float *post_win, c32 *fft_out, float *amp_out, float *ph_out,
+                            float *data_out, float *img, const c32 *cmask, float *sum_partial)
+{
+    if (P.family != kFamilyFBP || !fft_out || !amp_out || !ph_out || !data_out) return false;
+    FBArgs A{};
+    A.npix = npix; A.pre_win = pre_win; A.mask = mask ? mask : P.ones;
+    A.post_win = post_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
+    A.data_out = data_out; A.img = img;
+    A.cmask = reinterpret_cast<const cx *>(cmask);
+    A.sum_partial = sum_partial;
+    dispatch_fbp_pipe(st, P, A, &tilt);
+    return true;
+}
+
+size_t tilt_sum_rows(size_t npix)
+{
+    size_t g = (size_t)kNumCU * 4;
+    if (g > npix) g = npix;
+    return g < 1 ? 1 : g;
+}
+
+void launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out)
+{
+    const size_t rows = tilt_sum_rows(npix);
+    if (nt_out <= 5 * 256)  // every length of an FBP plan
+        THZ_LAUNCH(k_tilt_sum<5>, (unsigned)rows, 256, 0, st, npix, tilt.nt_in, nt_out, tilt.src, tilt.taper, tilt.ins, partial);
+    else
+        THZ_LAUNCH(k_tilt_sum<8>, (unsigned)rows, 256, 0, st, npix, tilt.nt_in, nt_out, tilt.src, tilt.taper, tilt.ins, partial);
+    launch_sum_rows_f64(st, partial, rows, (size_t)nt_out, out);
 }
 
 void launch_fd_mask(hipStream_t st, size_t npix, int nf, c32 *fft, float *amp, const float *mask)

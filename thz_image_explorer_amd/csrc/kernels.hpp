@@ -144,6 +144,23 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
                      const float *pre_win, const float *mask, const float *post_win, c32 *fft_out,
                      float *amp_out, float *ph_out, float *data_out, float *img, const c32 *cmask = nullptr,
                      float *sum_partial = nullptr, int band_lo4 = 0, int band_n = 0);
+// The Tilt stage's re-laying (launch_tilt) as a gather in the fused chain's forward loads (fft_fbp.hpp, TILT): the
+// source traces on their own axis, the tail taper, and every pixel's insert index on the extended axis
+struct FBPTilt {
+    const float *src;    // (npix, nt_in)
+    const float *taper;  // nt_in
+    const int *ins;      // npix
+    int nt_in;
+};
+// launch_pipeline of an FBP plan on traces that are re-laid while they are read (every output required); false, and
+// nothing launched, for any other plan
+bool launch_pipeline_tilted(hipStream_t st, const PlanDev &P, size_t npix, const FBPTilt &tilt, const float *pre_win,
+                            const float *mask, const float *post_win, c32 *fft_out, float *amp_out, float *ph_out,
+                            float *data_out, float *img, const c32 *cmask, float *sum_partial);
+// out[n] = sum over the pixels of the re-laid (tilted, tapered) samples, n < nt_out: tilt_sum_rows(npix) partial rows
+// of nt_out floats (sequential f32 per row), added in double
+size_t tilt_sum_rows(size_t npix);
+void launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out);
 void launch_fd_mask(hipStream_t st, size_t npix, int nf, c32 *fft, float *amp, const float *mask);
 void launch_fd_cmask(hipStream_t st, size_t npix, int nf, int nt, c32 *fft, float *amp,
                      const c32 *cmask);

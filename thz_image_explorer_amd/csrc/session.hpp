@@ -31,8 +31,21 @@ struct thz_session {
     float *d_vec = nullptr;                    // pre | mask | post multipliers (+ tilt scratch)
     float *h_vec = nullptr;                    // pinned host image of d_vec: the multipliers go up in one asynchronous copy
     size_t vec_floats = 0;
-    float *d_tilt = nullptr;                   // extended cube when tilt != 0 (kept while its size stays the same)
-    size_t tilt_floats = 0, ins_count = 0;
+    float *d_tilt = nullptr;                   // extended cube when tilt != 0 (kept while its size stays the same): built by
+    size_t tilt_floats = 0, ins_count = 0;     //   the staged path, or on demand behind a one-launch chain (session_extended_src)
+    std::vector<int32_t> ins_host;             // the insert indices d_ins holds (a recompute with the same plan does not copy them again)
+    // a tilted chain that ran as ONE launch from the untilted cube (FBP plans, thz_pipeline_tilted): what the launch
+    // gathered from, so that the extended traces can still be built for whoever needs them
+    bool tilt_fused = false;
+    const float *tilt_from = nullptr;          // d_raw or d_scaled
+    size_t tilt_nt_in = 0;
+    const float *d_taper = nullptr;            // the Tilt stage's tail taper (tilt_nt_in floats inside d_vec)
+    bool src_sum_own = false;                  // d_msum[0, nt_out) is THIS session's sum of source traces (a group adds the slabs')
+    // ... the re-laid traces' sum depends on the source cube, the scale factor and the tilt only (src_gen): kept, like
+    // d_rawsum, so that a recompute that moves another slider does not read the raw cube for it again
+    float *d_tiltsum = nullptr;
+    size_t tiltsum_floats = 0;
+    unsigned long tiltsum_gen = 0;             // the src_gen it belongs to, 0 = none
     std::vector<float> fd_real, fd_cmask;      // further Frequency-domain plugins: K14 real (nf), K13 complex (2 nf)
     thz_chain_cfg last_cfg{};                  // configuration of the last full recompute (decides whether a
     bool have_last_cfg = false;                // start position >= 6 may reuse the resident spectrum)
@@ -48,7 +61,8 @@ struct thz_session {
     bool msum_fast = false;      // the last recompute left its undivided sums in d_msum (want_means == 1)
     bool have_means = false;
     bool have_outputs = false;   // a recompute has run
-    const float *d_src = nullptr;  // what the fft stage read: d_raw, d_scaled or d_tilt (extended axis)
+    const float *d_src = nullptr;  // what the fft stage read: d_raw, d_scaled or d_tilt (extended axis); null while a
+                                   //   one-launch tilted chain's extended cube has not been asked for
     // ---- regions of interest (session_roi.cpp)
     std::vector<SessionRoi> rois;
     float *d_roi_sum = nullptr;    // [amplitudes R x nf | phases R x nf | stage-input traces R x nt | final traces R x nt]:
@@ -87,6 +101,10 @@ struct thz_session {
 // first half of a recompute: everything up to and including the fused launch, enqueued on the context's
 // stream (tail_only: chain positions >= 6 were served from the resident spectrum)
 int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, bool *tail_only);
+// The extended (re-laid) traces of a tilted chain that ran as one launch: the whole cube into d_tilt (and d_src) when
+// it is not there yet — for the regions of interest's source sums; never on the recompute path of a session without
+// regions.  A no-op for every other chain.
+int session_extended_src(thz_session *s);
 // Scaling over slab edges (group_session.cpp; math_tools.rs:273-301 adds a block's s x s inputs row by row): which rows
 // of the block grid slab `rank` of `world` owns when the raw grid's nx rows are cut by thz_host_slab.
 struct SlabScale {

@@ -98,7 +98,7 @@ void thz_session_destroy(thz_session *s)
     for (void *p : {(void *)s->d_raw, (void *)s->d_fft, (void *)s->d_amp, (void *)s->d_ph, (void *)s->d_data,
                     (void *)s->d_img, (void *)s->d_avg, (void *)s->d_vec, (void *)s->d_tilt, (void *)s->d_ins,
                     (void *)s->d_opacity, (void *)s->d_deconv, (void *)s->d_deconv_img, (void *)s->d_scaled,
-                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_carry_in, (void *)s->d_carry_out})
+                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out})
         if (p) (void)hipFree(p);
     if (s->h_vec) (void)hipHostFree(s->h_vec);
     session_roi_free(s);
@@ -254,6 +254,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     std::vector<float> tilt_taper;
     size_t nt_cur = s->nt;
     bool tilt_as_multiplier = false, tilted = false;
+    size_t tilt_nt_in = 0;  // tilted: the length of the traces in front of the Tilt stage
 
     // ---- scaling (math_tools.rs:242-310): s x s block means of the raw cube, / s^2 also on ragged
     // edges; dx, dy grow by s; identity when s <= 1 or when a side would vanish (:244-256)
@@ -340,23 +341,18 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
                 tilt_plan(time.data(), nt_cur, s->nx_cur, s->ny_cur, cfg->tilt_x_deg, cfg->tilt_y_deg, s->dx_cur, s->dy_cur,
                           new_time.data(), ins.data());
             }
-            if (s->tilt_floats != npix * nt2) {
-                s->tilt_floats = 0;
-                if (int rc = dev_alloc(ctx, &s->d_tilt, npix * nt2)) return rc;
-                s->tilt_floats = npix * nt2;
-            }
             if (s->ins_count != npix) {
                 s->ins_count = 0;
+                s->ins_host.clear();
                 if (int rc = dev_alloc(ctx, &s->d_ins, npix)) return rc;
                 s->ins_count = npix;
             }
             if (int rc = alloc_outputs(s, nt2)) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_ins, ins.data(), npix * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_vec, tilt_taper.data(), nt_cur * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            launch_tilt(ctx->stream, npix, (int)nt_cur, (int)nt2, src, s->d_vec, s->d_ins, s->d_tilt);
-            if (int rc = check_launch(ctx)) return rc;
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            src = s->d_tilt;
+            if (s->ins_host != ins) {  // (kept by the session: the copy below may still read it when this block ends)
+                s->ins_host.swap(ins);
+                HIP_TRY(ctx, hipMemcpyAsync(s->d_ins, s->ins_host.data(), npix * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+            }
+            tilt_nt_in = nt_cur;
             time = new_time;
             nt_cur = nt2;
             tilted = true;
@@ -412,6 +408,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // keep the masks 16-byte aligned for the kernels' vector reads
     float *d_mask = s->d_vec + ((2 * nt_cur + 3) & ~(size_t)3);
     float *d_cmask = d_mask + ((nf + 3) & ~(size_t)3);
+    float *d_taper = d_cmask + ((2 * nf + 3) & ~(size_t)3);  // tilted: the Tilt stage's tail taper, on the untilted axis
     {
         // one asynchronous copy out of the session's pinned image of d_vec (four pageable copies and a stream
         // synchronisation cost 0.1 ms per recompute, 5 % of a 128-row slab's); h_vec is not written again before
@@ -425,17 +422,38 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
             std::memcpy(h + (d_cmask - s->d_vec), s->fd_cmask.data(), 2 * nf * sizeof(float));
             used = (size_t)(d_cmask - s->d_vec) + 2 * nf;
         }
+        if (tilted) {
+            std::memcpy(h + (d_taper - s->d_vec), tilt_taper.data(), tilt_nt_in * sizeof(float));
+            used = (size_t)(d_taper - s->d_vec) + tilt_nt_in;
+        }
         HIP_TRY(ctx, hipMemcpyAsync(s->d_vec, h, used * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
 
+    // ---- a tilted cube: the lengths with an FBP plan (1025 ... 1280) run the whole chain as ONE launch from the
+    // untilted cube — the re-laying is a gather in the kernel's loads (thz_pipeline_tilted), no extended cube, no
+    // wait.  Every other plan re-lays the cube first (the staged path) and the chain reads the extended cube.
+    const bool fused_tilt = tilted && ctx->plan_d.family == kFamilyFBP;
+    const float *tilt_from = src;
+    if (tilted && !fused_tilt) {
+        if (s->tilt_floats != npix * nt_cur) {
+            s->tilt_floats = 0;
+            if (int rc = dev_alloc(ctx, &s->d_tilt, npix * nt_cur)) return rc;
+            s->tilt_floats = npix * nt_cur;
+        }
+        launch_tilt(ctx->stream, npix, (int)tilt_nt_in, (int)nt_cur, src, d_taper, s->d_ins, s->d_tilt);
+        if (int rc = check_launch(ctx)) return rc;
+        src = s->d_tilt;
+    }
+
     // ---- pixel means.  want_means == 1: amplitude / phase sums accumulated inside the fused launch, and
-    // avg_fft by linearity — every multiplier in front of the transform is the same for all pixels unless
-    // the cube was tilted, so mean_p(H FFT(w x_p)) = H FFT(w mean_p(x_p)): ONE extra transform instead of a
-    // pass over the spectra.  want_means == 2 (and any tilted cube): the reference's summation order
-    // (ndarray mean_axis twice, math_tools.rs:421-440), bit for bit, as three passes over the outputs.
-    s->msum_fast = cfg->want_means == 1 && !tilted;
-    // a group's slab of a tilted cube: sums that add up over the slabs — three passes over the outputs, any order
-    s->msum_passes = cfg->want_means == 1 && tilted && slab;
+    // avg_fft by linearity — every multiplier in front of the transform is the same for all pixels (a tilted cube:
+    // for all RE-LAID traces), so mean_p(H FFT(w x_p)) = H FFT(w mean_p(x_p)): ONE extra transform instead of a
+    // pass over the spectra.  want_means == 2 (and a tilted cube on the staged path): the reference's summation
+    // order (ndarray mean_axis twice, math_tools.rs:421-440), bit for bit, as three passes over the outputs.
+    s->msum_fast = cfg->want_means == 1 && (!tilted || fused_tilt);
+    // a group's slab of a tilted cube on the staged path: sums that add up over the slabs — three passes over the
+    // outputs, any order
+    s->msum_passes = cfg->want_means == 1 && tilted && !fused_tilt && slab;
     if (s->msum_fast || s->msum_passes) {
         if (s->msum_floats != nt_cur + 4 * nf) {
             s->msum_floats = 0;
@@ -443,11 +461,13 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
             s->msum_floats = nt_cur + 4 * nf;
         }
     }
-    if (s->msum_fast) {
+    if (s->msum_fast && !fused_tilt) {
         // Σ of the source traces: cached at upload for the raw cube, one small pass for a block-averaged one
+        // (the re-laid traces' comes out of thz_pipeline_tilted)
         if (src == s->d_raw) HIP_TRY(ctx, hipMemcpyAsync(s->d_msum, s->d_rawsum, nt_cur * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         else if (int rc = thz_pixel_sum(ctx, npix, nt_cur, 1, src, s->d_msum)) return rc;
     }
+    s->src_sum_own = s->msum_fast && (fused_tilt || src != s->d_raw);
     thz_pipeline_io io{};
     io.d_raw = src; io.d_pre_win = d_pre; io.d_fd_mask = d_mask; io.d_fd_cmask = s->fd_cmask.empty() ? nullptr : d_cmask;
     io.d_post_win = d_post; io.d_fft = s->d_fft; io.d_amp = s->d_amp; io.d_phase = s->d_ph; io.d_data_out = s->d_data;
@@ -456,18 +476,60 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // the band pass's own index range tells the fused kernel where its multiplier is zero (a further real plugin, K14,
     // only adds zeros inside)
     const bool band_known = cfg->fd_active && band_hi > band_lo && band_lo >= 0 && (size_t)band_hi <= nf;
-    if (int rc = pipeline_ex_band(ctx, npix, &io, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0)) return rc;
+    if (fused_tilt) {
+        io.d_raw = nullptr;
+        thz_tilt_src ts{};
+        ts.d_src = tilt_from; ts.nt_in = tilt_nt_in; ts.d_taper = d_taper; ts.d_insert_index = s->d_ins;
+        const bool sum_kept = s->msum_fast && s->tiltsum_gen == s->src_gen && s->tiltsum_floats == nt_cur;
+        ts.d_src_sum = s->msum_fast && !sum_kept ? s->d_msum : nullptr;
+        if (int rc = pipeline_tilted_band(ctx, npix, &io, &ts, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0)) return rc;
+        if (s->msum_fast) {  // (session_means scales d_msum in place and a group all-reduces it: the kept copy is apart)
+            if (!sum_kept && s->tiltsum_floats != nt_cur) {
+                s->tiltsum_floats = 0;
+                s->tiltsum_gen = 0;
+                if (int rc = dev_alloc(ctx, &s->d_tiltsum, nt_cur)) return rc;
+                s->tiltsum_floats = nt_cur;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(sum_kept ? s->d_msum : s->d_tiltsum, sum_kept ? s->d_tiltsum : s->d_msum, nt_cur * sizeof(float),
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+            s->tiltsum_gen = s->src_gen;
+        }
+    } else if (int rc = pipeline_ex_band(ctx, npix, &io, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0)) return rc;
     if (s->msum_passes) {
         if (int rc = thz_pixel_sum(ctx, npix, nf, 2, s->d_fft, s->d_msum + nt_cur)) return rc;
         if (int rc = thz_pixel_sum(ctx, npix, nf, 1, s->d_amp, s->d_msum + nt_cur + 2 * nf)) return rc;
         if (int rc = thz_pixel_sum(ctx, npix, nf, 1, s->d_ph, s->d_msum + nt_cur + 3 * nf)) return rc;
     }
+    // the extended traces of a one-launch tilted chain exist only once somebody asks (session_extended_src)
+    s->tilt_fused = fused_tilt;
+    s->tilt_from = tilt_from;
+    s->tilt_nt_in = tilt_nt_in;
+    s->d_taper = d_taper;
     s->have_means = false;
     s->have_outputs = true;
     s->deconv_current = false;  // the stage passes its input through unless it is the one updated
-    s->d_src = src;
+    s->d_src = fused_tilt ? nullptr : src;
     s->last_cfg = *cfg;
     s->have_last_cfg = true;
+    return THZ_OK;
+}
+
+int session_extended_src(thz_session *s)
+{
+    if (!s->tilt_fused || s->d_src) return THZ_OK;
+    thz_ctx *ctx = s->ctx;
+    const size_t npix = s->nx_cur * s->ny_cur, nt = s->nt_out;
+    if (s->tilt_floats != npix * nt) {
+        s->tilt_floats = 0;
+        if (int rc = dev_alloc(ctx, &s->d_tilt, npix * nt)) return rc;
+        s->tilt_floats = npix * nt;
+    }
+    {
+        StageTimer t(ctx, THZ_STAGE_TD_WINDOW);
+        launch_tilt(ctx->stream, npix, (int)s->tilt_nt_in, (int)nt, s->tilt_from, s->d_taper, s->d_ins, s->d_tilt);
+        if (int rc = check_launch(ctx)) return rc;
+    }
+    s->d_src = s->d_tilt;
     return THZ_OK;
 }
 
@@ -717,14 +779,21 @@ int thz_session_plot(thz_session *s, size_t px, size_t py, const thz_plot_out *o
     if (out->avg_phase_fft)
         if (int rc = thz_session_download(s, THZ_BUF_AVG_PHASES, 0, 1, out->avg_phase_fft)) return rc;
     if (out->signal_fft || out->phase_fft || out->avg_signal) {
-        // scratch behind the multipliers: [amp nf | phase nf | mean nt]
+        // scratch behind the multipliers: [amp nf | phase nf | mean nt | this pixel's re-laid trace nt]
         float *d_tmp = nullptr;
-        HIP_TRY(ctx, hipMalloc((void **)&d_tmp, (2 * nf + nt) * sizeof(float)));
+        HIP_TRY(ctx, hipMalloc((void **)&d_tmp, (2 * nf + 2 * nt) * sizeof(float)));
         int rc = THZ_OK;
         if (out->signal_fft || out->phase_fft) {
             // the fft stage's own amplitudes / phases (no band-pass yet): one trace through K1-K3 again
             if (ctx->time.size() != nt) rc = thz_set_time_axis(ctx, s->time_out.data(), nt);
-            const float *src = s->d_src + pix * nt;
+            const float *src = s->d_src ? s->d_src + pix * nt : nullptr;
+            if (!src) {  // a one-launch tilted chain left no extended cube: this pixel's trace alone
+                float *one = d_tmp + 2 * nf + nt;
+                launch_tilt(ctx->stream, 1, (int)s->tilt_nt_in, (int)nt, s->tilt_from + pix * s->tilt_nt_in, s->d_taper,
+                            s->d_ins + pix, one);
+                if (!rc) rc = check_launch(ctx);
+                src = one;
+            }
             if (!rc) rc = thz_fft(ctx, 1, src, s->d_vec /* pre */, nullptr, nullptr, nullptr, d_tmp, d_tmp + nf, nullptr);
             if (!rc && out->signal_fft) rc = thz_memcpy_d2h(ctx, out->signal_fft, d_tmp, nf * sizeof(float));
             if (!rc && out->phase_fft) rc = thz_memcpy_d2h(ctx, out->phase_fft, d_tmp + nf, nf * sizeof(float));

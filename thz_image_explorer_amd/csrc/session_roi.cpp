@@ -142,6 +142,9 @@ int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only_i
     const bool src_now = !data_only && (ordered || s->roi_src_gen != s->src_gen);
     s->roi_src_fresh = src_now;
     if (src_now) s->roi_src_gen = ordered ? 0 : s->src_gen;
+    // the source traces of a tilted chain that ran as one launch: the extended cube is built here, for the regions
+    if (src_now)
+        if (int rc = session_extended_src(s)) return rc;
     for (size_t r = 0; r < L.R; ++r) {
         const SessionRoi &roi = s->rois[r];
         float *o = s->d_roi_sum;
