@@ -586,7 +586,13 @@ int thz_session_deconvolve(thz_session *s, const thz_psf *psf, const thz_deconv_
 size_t thz_session_nt_out(const thz_session *s);
 int thz_session_time_out(const thz_session *s, float *time /* nt_out */);
 /* device pointer of a resident buffer; NULL if absent — every output buffer (everything but THZ_BUF_RAW
- * and THZ_BUF_IMG) is absent until a recompute has run after the latest upload */
+ * and THZ_BUF_IMG) is absent until a recompute has run after the latest upload.
+ * THZ_BUF_FFT and THZ_BUF_AMPLITUDES: the session is the only writer of these two arrays and, between
+ * recomputes, leaves in place the zeros that the Frequency Band Pass puts outside its range instead of
+ * storing them again.  A caller may write through the pointer until the NEXT recompute: every call of this
+ * function for one of the two makes that recompute store every bin.  Writing through a pointer obtained
+ * earlier, after a later recompute, is outside the contract — bins outside the band would keep what was
+ * written.  (The same holds for the sessions of a group, thz_group_session_member.) */
 void *thz_session_buffer(thz_session *s, int which);
 /* copies pixels [pix0, pix0+npix) of a per-pixel buffer (or the whole vector for
  * the AVG_* ones, pix0 = 0, npix = 1) to the host: the selected-pixel trace, a

@@ -6,8 +6,9 @@
 // mix or a property of one store pattern.  Pure-read / pure-write / copy
 // shapes are timed beside it as reference points.
 //
-//   hipcc --offload-arch=gfx950 -O3 -o gpurun_out/probe_shapes scripts/probe_shapes.hip
-//   ./gpurun_out/probe_shapes [npix_log2=18]
+//   hipcc --offload-arch=gfx950 -O3 -o probe_shapes scripts/probe_shapes.hip
+//   ./probe_shapes [npix_log2=18] [sweep: 2 = store path, 3 = fused chain's shape with / without the
+//                                             out-of-band stores [lo4 n]]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -394,6 +395,56 @@ __global__ __launch_bounds__(512) void k_coop_store(Bufs B)
     }
 }
 
+// S12: today's store shape of the fused chain (k_f<.., pipe>): amplitudes and phases group by group, then the
+// masked spectrum as sixteen 1 KiB stores in one burst (128 bins each, f_inverse_input), a barrier, the time
+// trace.  KEEP: the spectrum and amplitude stores outside the bins [lo4, lo4 + n) are left out — a quad of
+// bins is inside or outside as a whole, as in the kernel (phases and time trace stay whole).  Bin N is not
+// modelled (4 + 8 bytes per trace).
+template <bool KEEP>
+__global__ __launch_bounds__(512) void k_fused_shape(Bufs B, int lo4, int n)
+{
+    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    const size_t stride = (size_t)gridDim.x * wpb;
+    const size_t t0 = (size_t)blockIdx.x * wpb + (threadIdx.x >> 6);
+    const size_t iters = (B.npix + stride - 1) / stride;
+    f4a r[16], nx[16];
+    if (t0 < B.npix)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) nx[j] = *reinterpret_cast<const f4a *>(B.in + t0 * NT + 4 * (64 * j + lane));
+    for (size_t it = 0; it < iters; ++it) {
+        const size_t t = t0 + it * stride;
+        const bool on = t < B.npix;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) r[j] = nx[j];
+        if (on && t + stride < B.npix) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                nx[j] = *reinterpret_cast<const f4a *>(B.in + (t + stride) * NT + 4 * (64 * j + lane));
+        }
+        __syncthreads();
+        if (on) {
+            float *f = B.fft + t * (size_t)(2 * B.nf), *a = B.amp + t * (size_t)B.nf, *p = B.ph + t * (size_t)B.nf;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const int k = 256 * g + 4 * lane;
+                if (!KEEP || (unsigned)(k - lo4) < (unsigned)n) st<false>(a + k, r[g]);
+                st<false>(p + k, r[g + 8]);
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = 128 * j + 2 * lane;  // two bins = one 16-byte store
+                if (!KEEP || (unsigned)(k - lo4) < (unsigned)n) st<false>(f + 2 * k, r[j]);
+            }
+        }
+        __syncthreads();
+        if (on) {
+            float *o = B.out + t * NT;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) st<false>(o + 4 * (64 * j + lane), r[j]);
+        }
+    }
+}
+
 template <class F>
 static double time_ms(hipStream_t s, F launch, int reps = 7)
 {
@@ -483,6 +534,28 @@ int main(int argc, char **argv)
         report("S11 loads -> LDS -> block-cooperative contiguous stores, 256 x 512", time_ms(s, [&] { hipLaunchKernelGGL(k_coop_store, dim3(256), dim3(512), 8 * NT * 4, s, D); }), m_full);
         report("S11 same, 512 x 512", time_ms(s, [&] { hipLaunchKernelGGL(k_coop_store, dim3(512), dim3(512), 8 * NT * 4, s, D); }), m_full);
         report("S1 phased like k_f (prefetch), 256 x 512  [baseline again]", time_ms(s, [&] { hipLaunchKernelGGL((k_phased<false, true>), dim3(256), dim3(512), 0, s, D); }), m_full);
+        CK(hipFree(in));
+        CK(hipFree(big));
+        return 0;
+    }
+    if (argc > 2 && atoi(argv[2]) == 3) {
+        // the fused chain's shape whole and with the out-of-band spectrum / amplitude stores left out, alternating in
+        // one process: [lo4, lo4 + n) defaults to the default chain's band (0.2 - 5 THz at dt = 0.05 ps: bins 40 .. 1028)
+        const int lo4 = argc > 3 ? atoi(argv[3]) : 40, n = argc > 4 ? atoi(argv[4]) : 988;
+        const double m_keep = (double)npix * (4.0 * NT + 4.0 * (NT / 2) + 12.0 * n + 4.0 * NT);
+        printf("keep range: bins [%d, %d); bytes per trace %.0f whole, %.0f reduced (x %.3f)\n", lo4, lo4 + n,
+               m_full / npix, m_keep / npix, m_keep / m_full);
+        double lo[2] = {1e30, 1e30}, hi[2] = {0, 0};
+        for (int rep = 0; rep < 5; ++rep) {
+            const double a = time_ms(s, [&] { hipLaunchKernelGGL(k_fused_shape<false>, dim3(256), dim3(512), 0, s, D, 0, 0); });
+            const double b = time_ms(s, [&] { hipLaunchKernelGGL(k_fused_shape<true>, dim3(256), dim3(512), 0, s, D, lo4, n); });
+            report("S12 fused chain's shape, every store", a, m_full);
+            report("S12 same, out-of-band spectrum and amplitude stores left out", b, m_keep);
+            lo[0] = std::min(lo[0], a); hi[0] = std::max(hi[0], a);
+            lo[1] = std::min(lo[1], b); hi[1] = std::max(hi[1], b);
+        }
+        printf("whole   %.3f .. %.3f ms (spread %.2f %%)\nreduced %.3f .. %.3f ms (spread %.2f %%)\nreduced / whole = %.3f\n", lo[0], hi[0],
+               100.0 * (hi[0] - lo[0]) / lo[0], lo[1], hi[1], 100.0 * (hi[1] - lo[1]) / lo[1], (lo[1] + hi[1]) / (lo[0] + hi[0]));
         CK(hipFree(in));
         CK(hipFree(big));
         return 0;

@@ -465,9 +465,16 @@ int thz_pipeline_ex(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io)
 // thz_pipeline_ex for a caller that KNOWS where its real multiplier is not zero (the session: thz_host_fd_bandpass hands
 // the band's first and last bin back): every bin outside [band_lo, band_hi) is zero in io->d_fd_mask.  With a complex
 // multiplier the nt = 4096 kernel then stages only the band's bins (fft_f.hpp, kCfgBand).  0, 0: unknown.
-int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi)
+// keep: the bins of d_fft / d_amp the launch must store (ctx.hpp, KeepRange); null: every bin, as thz_pipeline_ex.
+int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi, KeepRange *keep)
 {
+    if (keep) keep->honoured = false;
     if (int rc = need_plan(ctx)) return rc;
+    int keep_lo4 = 0, keep_n = -1;  // every bin
+    if (keep && !keep->all && keep->hi >= keep->lo && keep->hi <= (size_t)ctx->plan_d.nf && pipeline_keeps_range(ctx->plan_d)) {
+        keep_lo4 = (int)(keep->lo & ~(size_t)3);
+        keep_n = (int)(((keep->hi + 3) & ~(size_t)3) - (size_t)keep_lo4);
+    }
     int band_lo4 = 0, band_n = 0;
     if (band_hi > band_lo && io && io->d_fd_cmask) {
         band_lo4 = (int)(band_lo & ~(size_t)3);
@@ -496,9 +503,10 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
         StageTimer t(ctx, THZ_STAGE_PIPELINE);
         launch_pipeline(ctx->stream, ctx->plan_d, npix, io->d_raw, io->d_pre_win, io->d_fd_mask, io->d_post_win,
                         reinterpret_cast<c32 *>(io->d_fft), io->d_amp, io->d_phase, io->d_data_out, io->d_img,
-                        reinterpret_cast<const c32 *>(io->d_fd_cmask), d_partial, band_lo4, band_n);
+                        reinterpret_cast<const c32 *>(io->d_fd_cmask), d_partial, band_lo4, band_n, keep_lo4, keep_n);
         if (int rc = check_launch(ctx)) return rc;
     }
+    if (keep) keep->honoured = pipeline_keeps_range(ctx->plan_d);  // (told "every bin" it obeyed that)
     if (!io->d_sums) return THZ_OK;
     if (d_partial) {
         StageTimer t(ctx, THZ_STAGE_MEAN);
@@ -511,8 +519,9 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
 
 // thz_pipeline_tilted with the real multiplier's non-zero range known (the session), as pipeline_ex_band
 int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src, size_t band_lo,
-                         size_t band_hi)
+                         size_t band_hi, KeepRange *keep)
 {
+    if (keep) keep->honoured = false;  // the one-launch form (FBP plans) writes everything
     if (int rc = need_plan(ctx)) return rc;
     if (!io || !io->d_data_out || !io->d_fft || !io->d_amp || !io->d_phase)
         return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: d_fft, d_amp, d_phase and d_data_out are required");
@@ -570,7 +579,7 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
     if (int rc = thz_tilt_apply(ctx, npix, src->d_src, src->nt_in, src->d_taper, src->d_insert_index, nt, ctx->tilt_scratch)) return rc;
     thz_pipeline_io staged = *io;
     staged.d_raw = ctx->tilt_scratch;
-    if (int rc = pipeline_ex_band(ctx, npix, &staged, band_lo, band_hi)) return rc;
+    if (int rc = pipeline_ex_band(ctx, npix, &staged, band_lo, band_hi, keep)) return rc;
     if (src->d_src_sum) return thz_pixel_sum(ctx, npix, nt, 1, ctx->tilt_scratch, src->d_src_sum);
     return THZ_OK;
 }

@@ -223,11 +223,20 @@ inline int need_plan(thz_ctx *ctx)
 }  // namespace thz_api
 using namespace thz_api;
 
+// The bins of d_fft / d_amp a fused launch has to store, for a caller that is the two arrays' only writer and knows
+// what they hold (the session): [lo, hi), widened to multiples of 4; the launch may leave every other bin of the two
+// arrays untouched.  all = true (the default): every bin.  `honoured` comes back true when the launch that ran is one
+// that obeys such a range (the F family), false when it wrote everything whatever it was told, or failed.
+struct KeepRange {
+    size_t lo = 0, hi = 0;
+    bool all = true;
+    bool honoured = false;
+};
 // api.cpp: thz_pipeline_ex with the real multiplier's non-zero range [band_lo, band_hi) known (0, 0: unknown)
-int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi);
+int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi, KeepRange *keep = nullptr);
 // api.cpp: thz_pipeline_tilted likewise
 int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, const thz_tilt_src *src, size_t band_lo,
-                         size_t band_hi);
+                         size_t band_hi, KeepRange *keep = nullptr);
 // api.cpp: order-free column sums over all rows (d_list null) or over the listed rows of d_arr
 int pixel_sum_rows(thz_ctx *ctx, const float *d_arr, const uint32_t *d_list, size_t npix, size_t L, float *d_out);
 

@@ -174,6 +174,8 @@ enum : int {
     kCfgCMask = 2,     // the per-bin multiplier is complex (K13, reference-pulse Wiener filter)
     kCfgSums = 4,      // the block also sums the stored amplitudes and unwrapped phases of its traces (FSums)
     kCfgBar = 8,       // the block's waves meet at a barrier before each store phase (FArgs::bar says which)
+    kCfgKeep = 32,     // fused chain: spectrum and amplitude stores obey FArgs' keep range (built beside the plain form: the
+                       // range-checked buffer stores cost a launch that writes everything 1.5-2.6 %, so it runs the plain one)
     kCfgBand = 16      // with kCfgCMask: the staged multiplier table covers only the bins FArgs::band_lo4 .. + band_n — where
                        // the real band pass is not zero — between two quads of zeros that every other bin's index is clamped
                        // to.  Half the table at the default 0.2-5 THz: what lets the nt = 4096 chain with the complex
@@ -555,6 +557,64 @@ __device__ __forceinline__ void load_f4(const float *p, float &a, float &b, floa
 }
 #endif
 
+// Keep range (fused chain, MODE == kPipe).  Outside the real band pass the chain stores X * 0 into fft_out and
+// |X| * 0 into amp_out — a fifth of the launch's bytes at the default 0.2 - 5 THz.  A caller that is the only writer of
+// the two arrays and knows that those bins already hold zeros in every row (the session, between recomputes) passes
+// the bins that may have changed as [keep_lo4, keep_lo4 + keep_n); the stores of every other bin are left out: the
+// amplitude quads of the spectrum epilogue, the 16-byte spectrum stores of f_inverse_input and lane 0's two stores of
+// bin N, each predicated on its own bins (edges are multiples of 4, so a quad / a bin pair is inside or outside as a
+// whole; see FRow for how).  Nothing else changes: phases, time trace, image and sums are computed and written as
+// before, from the same rounded products, and the stores that remain are issued in the same order.
+// A trace with a NaN or Inf sample is written in full, every time: its products X * 0 are NaN, not zero.  Every bin of
+// such a trace's transform is non-finite, so a wave ballot over the first group's X finds it (f_spectrum_epilogue).
+// NOT covered: a finite trace whose transform overflows to Inf in some bins only, none of them among the first 256 —
+// a full write stores NaN (Inf * 0) at those bins where they are out of band, a launch with a keep range leaves the
+// earlier value.  (Samples of 1e30 and more; the time trace of such a pixel is NaN either way.)
+constexpr int kFKeepAll = 1 << 30;
+
+// A window of an output row whose stores carry a per-lane predicate at no cost in control flow or registers: the
+// window is addressed as a raw buffer resource of `bytes` bytes, a store takes its byte offset from the window's start
+// as an unsigned number, and the memory pipeline's range check drops every store whose offset is not below `bytes` —
+// the bins behind the window, and, their offsets being "negative", the bins in front of it.  (An `if` around each of
+// the sixteen unrolled spectrum stores splits the pass into as many basic blocks, and the nt = 4096 kernels — at
+// 235-255 VGPRs — spill 114-222 of them; a compare and a select per store cost the nt = 1024 kernels their fourth
+// wave per SIMD.)  The whole offset goes in the VGPR (callers launder it): nothing is left for the instruction's
+// immediate offset, which the check would add to a wrapped value.
+#ifdef THZ_EMU
+struct FRow {
+    float *p;
+    unsigned bytes;
+};
+__device__ __forceinline__ FRow f_row(float *p, unsigned bytes) { return FRow{p, bytes}; }
+__device__ __forceinline__ void row_store_f4(const FRow &r, unsigned off, float a, float b, float c, float d)
+{
+    if (off < r.bytes) store_f4(r.p + off / 4, a, b, c, d);
+}
+__device__ __forceinline__ void row_store_f2(const FRow &r, unsigned off, float a, float b)
+{
+    if (off < r.bytes) { r.p[off / 4] = a; r.p[off / 4 + 1] = b; }
+}
+#else
+typedef __amdgpu_buffer_rsrc_t FRow;
+typedef unsigned thz_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned thz_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ FRow f_row(float *p, unsigned bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)bytes, 0x00020000);  // raw buffer, 32-bit data format
+}
+__device__ __forceinline__ void row_store_f4(const FRow &r, unsigned off, float a, float b, float c, float d)
+{
+    const thz_u4 v = {__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c),
+                      __builtin_bit_cast(unsigned, d)};
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 0);
+}
+__device__ __forceinline__ void row_store_f2(const FRow &r, unsigned off, float a, float b)
+{
+    const thz_u2 v = {__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b)};
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, 0);
+}
+#endif
+
 struct FArgs {
     size_t npix;
     const float *in;        // (npix, nt) raw traces            [fwd, pipeline]
@@ -575,6 +635,9 @@ struct FArgs {
                             // the staged complex multiplier; the real mask is zero at every bin outside
     float *sum_partial;     // (gridDim.x, 2 nf): every block's sums of its traces' stored amplitudes | unwrapped
                             // phases, written whole by the block (zeros if it had no trace); kCfgSums only
+    int keep_lo4 = 0, keep_n = kFKeepAll;  // fused chain: the launch must store spectrum and amplitudes of the bins
+                            // [keep_lo4, keep_lo4 + keep_n) (multiples of 4, >= 0) and may leave fft_out / amp_out
+                            // untouched outside (see "keep range" above); the default covers every bin
 };
 
 enum : int { kFwd = 0, kInv = 1, kPipe = 2 };
@@ -823,11 +886,17 @@ struct FSums {
 // STORE_FFT = false (fused chain): the masked spectrum is stored by f_inverse_input, which forms the same products
 // X m (X H) anyway and holds them two adjacent bins per lane — sixteen 1 KiB stores in one short burst instead of two
 // per group spread over the whole epilogue; only the Nyquist bin is still stored here.
-template <class P, bool AMP_PHASE, bool CMASK = false, bool SUMS = false, bool WC = false, bool STORE_FFT = true, bool BAND = false>
+// KEEP (fused chain): amplitudes and bin N are stored inside the keep range only; keep_lo / keep_n come back as the
+// range this trace's stores obey — FArgs' own, or every bin for a non-finite trace — for f_inverse_input.
+template <class P, bool AMP_PHASE, bool CMASK = false, bool SUMS = false, bool WC = false, bool STORE_FFT = true, bool BAND = false,
+          bool KEEP = false>
 __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, const cx *wg_s,
                                                     const float *mask, size_t p, const FArgs &A,
-                                                    int lane, FSums<P> *sums = nullptr)
+                                                    int lane, FSums<P> *sums = nullptr, int *keep_lo = nullptr,
+                                                    int *keep_n = nullptr)
 {
+    static_assert(!KEEP || !STORE_FFT, "the keep range is the fused chain's");
+    int klo = A.keep_lo4, kn = A.keep_n;
     static_assert(!BAND || CMASK, "the band-limited table is the complex multiplier's");
     const int band_off = 4 - A.band_lo4, band_cap = A.band_n + 4;  // BAND: table entry of bin k = clamp(k + band_off, 0, band_cap)
     static_assert(!SUMS || AMP_PHASE, "the sums are those of the amplitudes and phases");
@@ -888,6 +957,21 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
 #pragma unroll
             for (int c = 0; c < 4; ++c) X[c] = zf[fb[c]];
         }
+        if constexpr (KEEP) {
+            if (g == 0) {
+                // a NaN or Inf sample makes every bin non-finite: exponent bits all ones somewhere in this group
+                bool bad = false;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    bad = bad || abs_bits(X[c].x) >= 0x7f800000u || abs_bits(X[c].y) >= 0x7f800000u;
+                if (wave_any(bad)) {
+                    klo = 0;
+                    kn = kFKeepAll;
+                }
+            }
+        }
+        // KEEP: the amplitude quads go to the keep range's bins below N as a window (FRow; bin N: lane 0, below)
+        const unsigned amp_bytes = kn < N - klo ? 4u * (unsigned)kn : (N > klo ? 4u * (unsigned)(N - klo) : 0u);
         float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // the stored amplitudes (AMP_PHASE)
         if constexpr (CMASK) {
             cx Y[4];
@@ -905,7 +989,8 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
             if constexpr (AMP_PHASE) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) a[c] = fast_sqrt(fmaf(Y[c].x, Y[c].x, Y[c].y * Y[c].y));
-                store_f4(A.amp_out + p * nf + k0, a[0], a[1], a[2], a[3]);
+                if constexpr (KEEP) row_store_f4(f_row(A.amp_out + p * nf + klo, amp_bytes), (unsigned)launder_v(4 * (k0 - klo)), a[0], a[1], a[2], a[3]);
+                else store_f4(A.amp_out + p * nf + k0, a[0], a[1], a[2], a[3]);
             }
             if constexpr (STORE_FFT) {
                 if (g == 0 && lane == 0) Y[0].y = 0.0f;  // bin 0
@@ -922,7 +1007,8 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
             if constexpr (AMP_PHASE) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) a[c] = fast_sqrt(fmaf(X[c].x, X[c].x, X[c].y * X[c].y)) * m[c];
-                store_f4(A.amp_out + p * nf + k0, a[0], a[1], a[2], a[3]);
+                if constexpr (KEEP) row_store_f4(f_row(A.amp_out + p * nf + klo, amp_bytes), (unsigned)launder_v(4 * (k0 - klo)), a[0], a[1], a[2], a[3]);
+                else store_f4(A.amp_out + p * nf + k0, a[0], a[1], a[2], a[3]);
             }
             if constexpr (STORE_FFT) {
                 float *f = reinterpret_cast<float *>(A.fft_out + p * nf + k0);
@@ -973,21 +1059,28 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
             if constexpr (SUMS) sums->group(g, a, y, lane);
         }
     }
+    if constexpr (KEEP) {
+        *keep_lo = klo;
+        *keep_n = kn;
+    }
     // Nyquist bin k = N (real): lane 0
     if (lane == 0) {
+        const bool keep_nyq = !KEEP || (unsigned)(N - klo) < (unsigned)kn;
         const float xr = buf[N].x;
         float aN;
         if constexpr (CMASK) {
             const cx hN = reinterpret_cast<const cx *>(mask)[BAND ? f_band_index(N + band_off, band_cap) : N];
             const cx yN = cx{xr * hN.x, xr * hN.y};
-            A.fft_out[p * nf + N] = cx{yN.x, 0.0f};
+            if (keep_nyq) A.fft_out[p * nf + N] = cx{yN.x, 0.0f};
             aN = fast_sqrt(fmaf(yN.x, yN.x, yN.y * yN.y));
         } else {
             const float mN = mask[N];
-            A.fft_out[p * nf + N] = cx{xr * mN, 0.0f};
+            if (keep_nyq) A.fft_out[p * nf + N] = cx{xr * mN, 0.0f};
             aN = fabsf(xr) * mN;
         }
-        if constexpr (AMP_PHASE) A.amp_out[p * nf + N] = aN;
+        if constexpr (AMP_PHASE) {
+            if (keep_nyq) A.amp_out[p * nf + N] = aN;
+        }
         if constexpr (want_phase) {
             const float phn = fast_atan2f(0.0f, xr);
             float d = phn - last_raw;
@@ -1009,11 +1102,13 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
 // CMASK (with MASKED): the multiplier is complex, mask points to nf cx; X[0] H[0] and X[N] H[N] lose their
 // imaginary parts after the multiply.
 // STORE (fused chain, with MASKED): fft_row = the trace's row of the spectrum output; the masked bins n < N — the
-// values the inverse transform is built from, to the bit — are stored from here (bin N: the spectrum epilogue).
-template <class P, bool MASKED, bool CMASK = false, bool WC = false, bool STORE = false, bool BAND = false>
+// values the inverse transform is built from, to the bit — are stored from here (bin N: the spectrum epilogue), those
+// of the bins [keep_lo, keep_lo + keep_n) only (FArgs' keep range, as f_spectrum_epilogue hands it on).
+template <class P, bool MASKED, bool CMASK = false, bool WC = false, bool STORE = false, bool BAND = false, bool KEEP = false>
 __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, const cx *wg_s,
                                                 const float *__restrict__ mask, int lane,
-                                                cx (&r)[P::C1][P::R1], cx *fft_row = nullptr, int band_off = 0, int band_cap = 0)
+                                                cx (&r)[P::C1][P::R1], cx *fft_row = nullptr, int band_off = 0, int band_cap = 0,
+                                                int keep_lo = 0, int keep_n = kFKeepAll)
 {
     // the masked values are stored AND consumed: no product of this function may be fused into the split's adds
     // (the stand-alone inverse must land on the same samples from the stored spectrum, bit for bit)
@@ -1049,7 +1144,11 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
     constexpr int TOP = M1 * (R1 - 1) + C1 - 1;
     const int mk_f = launder_v(C1 * lane);                 // mask[n]     = mask[mk_f + M1 j1 + c]
     const int mk_r = launder_v(N - TOP - C1 * lane);       // mask[N - n] = mask[mk_r + TOP - (M1 j1 + c)]
-    float *frow = reinterpret_cast<float *>(fft_row) + 2 * mk_f;
+    // STORE: the keep range's bins below N as the window (FRow); rel: byte offset of the lane's bin of j1 = 0 in it
+    const int keep_bins = keep_n < N - keep_lo ? keep_n : N - keep_lo;
+    const FRow frow = f_row(reinterpret_cast<float *>(fft_row + (STORE && KEEP ? keep_lo : 0)), STORE && KEEP && keep_bins > 0 ? 8u * (unsigned)keep_bins : 0u);
+    float *frow_all = reinterpret_cast<float *>(fft_row) + 2 * mk_f;  // !KEEP: every bin, plain stores
+    const int rel = KEEP ? launder_v(8 * (mk_f - keep_lo)) : 0;
 #pragma unroll
     for (int j1 = 0; j1 < R1; ++j1) {
         const cx wgc = cx_conj(wg_s[j1]);  // conj(w2n[M1 j1]), wave-uniform
@@ -1090,8 +1189,15 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
             r[c][j1] = c2r_swapped(xk, xn, wc);
         }
         if constexpr (STORE) {
-            if constexpr (C1 == 2) store_f4(frow + 2 * M1 * j1, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
-            else *reinterpret_cast<float2 *>(frow + 2 * M1 * j1) = make_float2(kept[0].x, kept[0].y);
+            // bins M1 j1 + C1 lane (+ 1), 8 bytes each; the offset is formed here, not sixteen of them up front
+            if constexpr (KEEP) {
+                const unsigned at = (unsigned)launder_after(rel + 8 * M1 * j1, kept[0].x);
+                if constexpr (C1 == 2) row_store_f4(frow, at, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
+                else row_store_f2(frow, at, kept[0].x, kept[0].y);
+            } else {
+                if constexpr (C1 == 2) store_f4(frow_all + 2 * M1 * j1, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
+                else *reinterpret_cast<float2 *>(frow_all + 2 * M1 * j1) = make_float2(kept[0].x, kept[0].y);
+            }
         }
         if ((j1 & 1) == 1) THZ_SCHED_FENCE();
     }
@@ -1208,8 +1314,10 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     constexpr bool CMASK = (CFG & kCfgCMask) != 0 && MODE != kInv;
     constexpr bool SUMS = (CFG & kCfgSums) != 0;
     constexpr bool BAND = (CFG & kCfgBand) != 0 && CMASK;
+    constexpr bool KEEP = (CFG & kCfgKeep) != 0;
+    static_assert(!KEEP || MODE == kPipe, "the keep range is the fused chain's");
     static_assert(!SUMS || (MODE == kPipe && AMP_PHASE && (CFG & kCfgBar) != 0), "sums: fused chain, block-uniform trace loop");
-    constexpr int ME = P::mask_entries(CFG);
+    constexpr int ME = P::mask_entries(CFG & ~kCfgKeep);
     const int nf = N + 1;
     const int lane = lane_id();
     const int wib = THZ_UNIFORM((int)(threadIdx.x >> 6));
@@ -1415,13 +1523,14 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     // spectrum stores (+ the inverse transform of the fused chain)
     auto part_b = [&]() {
         if constexpr (MODE != kInv) {
-            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND>(buf, launder_uniform((const cx *)w2n_s),
-                                                                              launder_uniform((const cx *)wg_s), mask_l, p, A, lane,
-                                                                              &sums);
+            int keep_lo = 0, keep_n = kFKeepAll;  // MODE == kPipe: this trace's keep range (every bin if it is not finite)
+            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND, KEEP>(
+                buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, p, A, lane, &sums, &keep_lo, &keep_n);
             if constexpr (MODE == kPipe) {
                 cx r[C1][R1];
-                f_inverse_input<P, true, CMASK, TC, true, BAND>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
-                                                                mask_l, lane, r, A.fft_out + p * nf, 4 - A.band_lo4, A.band_n + 4);
+                f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
+                                                                mask_l, lane, r, A.fft_out + p * nf, 4 - A.band_lo4, A.band_n + 4,
+                                                                THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
                 wave_sync();  // every lane has read Z before the core overwrites buf
                 f_core_pass1<P, TC>(r, buf, t1, ad, lane);
                 if (p + stride < A.npix) f_load_raw<P>(A.in + (p + stride) * NT, lane, raw);

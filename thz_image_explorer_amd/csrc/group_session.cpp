@@ -115,7 +115,7 @@ static int gather_buf(thz_group_session *gs, int which, size_t per_pix, float **
     std::vector<const float *> send;
     std::vector<size_t> counts((size_t)g->world);
     for (int q = 0; q < g->world; ++q) counts[(size_t)q] = gs->cur_rows[(size_t)q] * gs->cur_ny * per_pix;
-    for (thz_session *s : gs->sess) send.push_back(static_cast<const float *>(thz_session_buffer(s, which)));
+    for (thz_session *s : gs->sess) send.push_back(static_cast<const float *>(session_buffer_ro(s, which)));
     const size_t need = gs->cur_pix() * per_pix;
     if (gs->root_local >= 0 && (!*d_dst || *cap < need)) {  // (a tilted cube's outputs are longer than the raw traces)
         GHIP_TRY(g, hipSetDevice(g->m[(size_t)gs->root_local].ctx->device));

@@ -2430,6 +2430,23 @@ static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool am
         // the fused chain always writes amplitudes and phases
         int cfg = ((MODE == kPipe || amp_phase) ? kCfgAmpPhase : 0) | (A.cmask ? kCfgCMask : 0) | bar;
         if constexpr (MODE == kPipe) {
+            // a launch told to leave bins alone runs the kCfgKeep build of its kernel; one that writes everything the plain one
+            if (A.keep_lo4 > 0 || A.keep_n < kFKeepAll) {
+                constexpr int K = kCfgKeep | kCfgAmpPhase;
+                if (A.sum_partial) {
+                    if (A.cmask && f_band_fits(P, A.band_lo4, A.band_n))
+                        launch_f<FPlan4096, MODE, K | kCfgBar | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
+                    else if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask | kCfgSums>(st, P, A);
+                    else dispatch_f_size<MODE, K | kCfgBar | kCfgSums>(st, P, A);
+                } else if (bar) {
+                    if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask>(st, P, A);
+                    else dispatch_f_size<MODE, K | kCfgBar>(st, P, A);
+                } else {
+                    if (A.cmask) dispatch_f_size<MODE, K | kCfgCMask>(st, P, A);
+                    else dispatch_f_size<MODE, K>(st, P, A);
+                }
+                return;
+            }
             if (A.sum_partial) {  // pixel sums inside the launch: the block-uniform trace loop of the barrier builds
                 if (A.cmask && f_band_fits(P, A.band_lo4, A.band_n))   // nt = 4096: the band-limited table keeps the eighth wave
                     launch_f<FPlan4096, MODE, kCfgBar | kCfgAmpPhase | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
@@ -2899,10 +2916,13 @@ size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4
     }
 }
 
+// the fused chains that honour a keep range: the F family's (with fft_out, amp_out and ph_out, which its callers require)
+bool pipeline_keeps_range(const PlanDev &P) { return P.family == kFamilyF; }
+
 void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float *raw,
                      const float *pre_win, const float *mask, const float *post_win, c32 *fft_out,
                      float *amp_out, float *ph_out, float *data_out, float *img, const c32 *cmask,
-                     float *sum_partial, int band_lo4, int band_n)
+                     float *sum_partial, int band_lo4, int band_n, int keep_lo4, int keep_n)
 {
     if (P.family == kFamilyF && fft_out && amp_out && ph_out) {
         FArgs A{};
@@ -2912,6 +2932,10 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
         A.data_out = data_out; A.img = img;
         A.sum_partial = sum_partial;  // pipeline_sum_rows(P, npix, cmask) rows, or null
         A.band_lo4 = band_lo4; A.band_n = band_n;
+        if (keep_n >= 0 && keep_lo4 >= 0 && keep_lo4 % 4 == 0 && keep_n % 4 == 0) {  // anything else: every bin (FArgs' default)
+            A.keep_lo4 = keep_lo4 < P.nf ? keep_lo4 : (P.nf + 3) & ~3;
+            A.keep_n = keep_n < kFKeepAll ? keep_n : kFKeepAll;
+        }
         dispatch_f<kPipe>(st, P, A, true);
         return;
     }

@@ -139,11 +139,15 @@ void launch_fft_inv(hipStream_t st, const PlanDev &P, size_t npix, const c32 *ff
 // (launch_sum_axis0 over the rows) makes the pixel sums of them
 // band_lo4 / band_n (multiples of 4; 0, 0 = unknown): the bins outside [band_lo4, band_lo4 + band_n) are zero in `mask` —
 // lets the nt = 4096 chain with a complex multiplier and the sums stage a band-limited table (fft_f.hpp, kCfgBand)
+// keep_lo4 / keep_n (multiples of 4): the launch must store the bins [keep_lo4, keep_lo4 + keep_n) of fft_out and
+// amp_out and may leave the others untouched (fft_f.hpp, "keep range"); keep_n < 0 = every bin.  Honoured by the plans
+// pipeline_keeps_range() names; every other plan writes everything.
 size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4 = 0, int band_n = 0);
+bool pipeline_keeps_range(const PlanDev &P);
 void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float *raw,
                      const float *pre_win, const float *mask, const float *post_win, c32 *fft_out,
                      float *amp_out, float *ph_out, float *data_out, float *img, const c32 *cmask = nullptr,
-                     float *sum_partial = nullptr, int band_lo4 = 0, int band_n = 0);
+                     float *sum_partial = nullptr, int band_lo4 = 0, int band_n = 0, int keep_lo4 = 0, int keep_n = -1);
 // The Tilt stage's re-laying (launch_tilt) as a gather in the fused chain's forward loads (fft_fbp.hpp, TILT): the
 // source traces on their own axis, the tail taper, and every pixel's insert index on the extended axis
 struct FBPTilt {

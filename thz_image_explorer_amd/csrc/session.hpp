@@ -61,6 +61,14 @@ struct thz_session {
     bool msum_fast = false;      // the last recompute left its undivided sums in d_msum (want_means == 1)
     bool have_means = false;
     bool have_outputs = false;   // a recompute has run
+    // Which bins of d_fft / d_amp hold zeros in every row: those outside [zero_lo, zero_hi), left there by fused
+    // launches whose multiplier is zero outside the Frequency Band Pass's range — the next such launch stores only the
+    // hull of its own range and this one (fft_f.hpp, "keep range").  zeros_known = false: nothing is known, the next
+    // launch writes every bin.  session_enqueue is the two arrays' only writer; whatever may change their contents or
+    // their shape behind its back drops the knowledge (session_forget_zeros).
+    bool zeros_known = false;
+    size_t zero_lo = 0, zero_hi = 0;
+    unsigned long zero_gen = 0;  // the src_gen the knowledge belongs to
     const float *d_src = nullptr;  // what the fft stage read: d_raw, d_scaled or d_tilt (extended axis); null while a
                                    //   one-launch tilted chain's extended cube has not been asked for
     // ---- regions of interest (session_roi.cpp)
@@ -101,6 +109,9 @@ struct thz_session {
 // first half of a recompute: everything up to and including the fused launch, enqueued on the context's
 // stream (tail_only: chain positions >= 6 were served from the resident spectrum)
 int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, bool *tail_only);
+// thz_session_buffer for readers inside the library: hands out no right to write, so the session keeps what it knows
+// of its spectrum's zeros
+const void *session_buffer_ro(thz_session *s, int which);
 // The extended (re-laid) traces of a tilted chain that ran as one launch: the whole cube into d_tilt (and d_src) when
 // it is not there yet — for the regions of interest's source sums; never on the recompute path of a session without
 // regions.  A no-op for every other chain.

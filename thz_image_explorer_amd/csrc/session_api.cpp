@@ -3,6 +3,8 @@
 #include "session.hpp"
 #include "host_windows.hpp"
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 
 using namespace thz;
@@ -293,6 +295,12 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
         ++s->src_gen;
         s->last_sf = (int)sf; s->last_tilt_active = cfg->tilt_active; s->last_tilt_x = cfg->tilt_x_deg; s->last_tilt_y = cfg->tilt_y_deg;
     }
+    // what is known of the zeros in d_fft / d_amp (session.hpp) holds for this recompute if it is about these source
+    // traces and — checked at the launch — these buffers; it is void until this recompute's launch has succeeded
+    const bool zeros_before = s->zeros_known && s->zero_gen == s->src_gen;
+    const float *const fft_before = s->d_fft;
+    const size_t pix_before = s->out_pix, nt_before = s->nt_out;
+    s->zeros_known = false;
     s->have_outputs = false;  // the grid may change under the buffers below
     s->have_last_cfg = false;
     s->deconv_current = false;
@@ -476,13 +484,30 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // the band pass's own index range tells the fused kernel where its multiplier is zero (a further real plugin, K14,
     // only adds zeros inside)
     const bool band_known = cfg->fd_active && band_hi > band_lo && band_lo >= 0 && (size_t)band_hi <= nf;
+    // The multiplier is zero outside [band_lo, band_hi) — checked on the vector itself, a plugin's NaN or Inf times
+    // the band pass's zero is not one; a complex multiplier must be finite there — so this launch leaves zeros in
+    // d_fft / d_amp outside that range, and where the launch before it did the same only the hull of the two ranges
+    // has to be stored (fft_f.hpp, "keep range").  THZ_F_KEEP_ZEROS=0: developer knob, every launch writes everything.
+    bool zero_outside = band_known;
+    if (const char *e = getenv("THZ_F_KEEP_ZEROS")) zero_outside = zero_outside && atoi(e) != 0;
+    for (size_t k = 0; zero_outside && k < nf; ++k) {
+        if (k >= (size_t)band_lo && k < (size_t)band_hi) continue;
+        zero_outside = mask[k] == 0.0f
+                       && (s->fd_cmask.empty() || (std::isfinite(s->fd_cmask[2 * k]) && std::isfinite(s->fd_cmask[2 * k + 1])));
+    }
+    KeepRange keep;
+    if (zero_outside && zeros_before && s->d_fft == fft_before && s->out_pix == pix_before && s->nt_out == nt_before) {
+        keep.all = false;
+        keep.lo = std::min((size_t)band_lo, s->zero_lo);
+        keep.hi = std::max((size_t)band_hi, s->zero_hi);
+    }
     if (fused_tilt) {
         io.d_raw = nullptr;
         thz_tilt_src ts{};
         ts.d_src = tilt_from; ts.nt_in = tilt_nt_in; ts.d_taper = d_taper; ts.d_insert_index = s->d_ins;
         const bool sum_kept = s->msum_fast && s->tiltsum_gen == s->src_gen && s->tiltsum_floats == nt_cur;
         ts.d_src_sum = s->msum_fast && !sum_kept ? s->d_msum : nullptr;
-        if (int rc = pipeline_tilted_band(ctx, npix, &io, &ts, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0)) return rc;
+        if (int rc = pipeline_tilted_band(ctx, npix, &io, &ts, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0, &keep)) return rc;
         if (s->msum_fast) {  // (session_means scales d_msum in place and a group all-reduces it: the kept copy is apart)
             if (!sum_kept && s->tiltsum_floats != nt_cur) {
                 s->tiltsum_floats = 0;
@@ -494,7 +519,12 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
                                         hipMemcpyDeviceToDevice, ctx->stream));
             s->tiltsum_gen = s->src_gen;
         }
-    } else if (int rc = pipeline_ex_band(ctx, npix, &io, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0)) return rc;
+    } else if (int rc = pipeline_ex_band(ctx, npix, &io, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0, &keep)) return rc;
+    if (zero_outside && keep.honoured) {  // (a launch of a family that was not told leaves nothing known)
+        s->zeros_known = true;
+        s->zero_lo = (size_t)band_lo; s->zero_hi = (size_t)band_hi;
+        s->zero_gen = s->src_gen;
+    }
     if (s->msum_passes) {
         if (int rc = thz_pixel_sum(ctx, npix, nf, 2, s->d_fft, s->d_msum + nt_cur)) return rc;
         if (int rc = thz_pixel_sum(ctx, npix, nf, 1, s->d_amp, s->d_msum + nt_cur + 2 * nf)) return rc;
@@ -660,6 +690,16 @@ int thz_session_time_out(const thz_session *s, float *time)
 
 void *thz_session_buffer(thz_session *s, int which)
 {
+    // a caller that holds the pointer may write: nothing is known of the two arrays' zeros any more (session.hpp)
+    if (s && (which == THZ_BUF_FFT || which == THZ_BUF_AMPLITUDES)) s->zeros_known = false;
+    return const_cast<void *>(session_buffer_ro(s, which));
+}
+
+}  // extern "C"
+
+// thz_session_buffer for the library's own readers (downloads, a group's gathers)
+const void *session_buffer_ro(thz_session *s, int which)
+{
     if (!s) return nullptr;
     const size_t nf = s->nf_out;
     // Before the first recompute (and between an upload and the next recompute) the output buffers hold
@@ -682,11 +722,13 @@ void *thz_session_buffer(thz_session *s, int which)
     }
 }
 
+extern "C" {
+
 int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, void *dst)
 {
     if (!s || !dst) return THZ_ERR_INVALID;
     thz_ctx *ctx = s->ctx;
-    const float *base = static_cast<const float *>(thz_session_buffer(s, which));
+    const float *base = static_cast<const float *>(session_buffer_ro(s, which));
     if (!base) return fail(ctx, THZ_ERR_NOT_READY, "thz_session_download: buffer not available");
     size_t per = 0;  // floats per pixel
     // per-pixel outputs were allocated for out_pix pixels by the recompute that filled them; the image has

@@ -199,6 +199,9 @@ __device__ __forceinline__ float launder_f(float x)
 // value known to be the same in every lane of the wave -> keep it in an SGPR
 #define THZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 
+// does the predicate hold in any lane of the wave?  (wave-uniform result)
+__device__ __forceinline__ bool wave_any(bool pred) { return __builtin_amdgcn_ballot_w64(pred) != 0; }
+
 #define THZ_LAUNCH(kernel, grid, block, lds_bytes, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), (lds_bytes), (stream), __VA_ARGS__)
 
@@ -210,6 +213,8 @@ inline unsigned wave_reduce_max_u32(unsigned v)
     for (int m = 1; m < kWave; m <<= 1) v = umax(v, __builtin_bit_cast(unsigned, wave_shfl_xor(__builtin_bit_cast(float, v), m)));
     return v;
 }
+
+inline bool wave_any(bool pred) { return wave_reduce_max_u32(pred ? 1u : 0u) != 0u; }
 
 #endif  // !THZ_EMU
 
