@@ -277,27 +277,73 @@ int emu_td_window(size_t npix, int nt, const float *in, const float *win, float 
     return 0;
 }
 
-// thz_pixel_sum's launch sequence (api.cpp): column sums of an (nrows, L) array
+// thz_pixel_sum's launch sequence (launch_pixel_sum_rows, what api.cpp's pixel_sum_rows runs): column sums of an
+// (nrows, L) array, or of its rows list[0 .. nrows).  The workspace starts as NaN: a partial entry that is read
+// without having been written shows in the result.
+int emu_pixel_sum_list(size_t nrows, size_t L, const float *arr, const uint32_t *list, float *out)
+{
+    std::vector<float> ws(pixel_sum_ws_floats(nrows, L), std::nanf(""));
+    launch_pixel_sum_rows(nullptr, arr, list, nrows, L, ws.data(), out);
+    return 0;
+}
+
 int emu_pixel_sum(size_t nrows, size_t L, const float *arr, float *out)
 {
-    if (nrows < 64) {
-        launch_sum_axis0(nullptr, arr, nrows, L, 0.0f, out);
-        return 0;
-    }
-    const size_t max_groups = 2048, mid_groups = 32;
-    std::vector<float> part((max_groups + mid_groups) * L);
-    float *part2 = part.data() + max_groups * L;
-    size_t groups = launch_colsum_partial(nullptr, arr, nrows, L, part.data(), max_groups);
-    if (groups == 0) {
-        launch_sum_axis0(nullptr, arr, nrows, L, 0.0f, out);
-        return 1;
-    }
-    const float *src = part.data();
-    if (groups > 4 * mid_groups) {
-        groups = launch_colsum_partial(nullptr, part.data(), groups, L, part2, mid_groups);
-        src = part2;
-    }
-    launch_sum_axis0(nullptr, src, groups, L, 0.0f, out);
+    return emu_pixel_sum_list(nrows, L, arr, nullptr, out);
+}
+
+// one level of the pixel sums on its own, with the number of row groups capped by the caller: few groups give each
+// block many rows at a small array (more than 64 x groups rows: a second trip of the ragged tail's lanes).  `partial`:
+// max_groups rows of L floats; returns the number of rows written
+size_t emu_colsum_partial(size_t nrows, size_t L, const float *arr, const uint32_t *list, size_t max_groups, float *partial)
+{
+    return launch_colsum_partial(nullptr, arr, nrows, L, partial, max_groups, list);
+}
+
+int emu_colsum_kc(size_t L)
+{
+    return colsum_partial_kc(L);
+}
+
+int emu_sum_axis0(const float *arr, size_t n0, size_t inner, float div, const float *carry, float *out)
+{
+    launch_sum_axis0(nullptr, arr, n0, inner, div, out, carry);
+    return 0;
+}
+
+int emu_sum_rows_f64(const float *arr, size_t n0, size_t inner, float *out)
+{
+    launch_sum_rows_f64(nullptr, arr, n0, inner, out);
+    return 0;
+}
+
+int emu_scale_rows_partial(const float *arr, size_t m, size_t ny, size_t L, size_t s, const float *carry, float div, float *out)
+{
+    launch_scale_rows_partial(nullptr, arr, m, ny, L, s, carry, div, out);
+    return 0;
+}
+
+int emu_gather_sum_w(const float *arr, size_t len, const uint32_t *list, uint32_t count, float div, const float *w1,
+                     const float *w2, const float *w3, float *out)
+{
+    launch_gather_sum_w(nullptr, arr, len, list, count, div, w1, w2, w3, out);
+    return 0;
+}
+
+// column sums of the cube emu_tilt writes, with the partial rows sized as the product sizes them; returns the number of
+// partial rows, or -2 when launch_tilt_sum refuses the length (nothing launched, `out` untouched)
+int emu_tilt_sum(size_t npix, int nt_in, int nt_out, const float *in, const float *taper, const int *ins, float *out)
+{
+    const size_t rows = tilt_sum_rows(npix);
+    std::vector<float> partial(rows * (size_t)(nt_out > 0 ? nt_out : 0), std::nanf(""));  // every entry must be written by the kernel
+    const FBPTilt T{in, taper, ins, nt_in};
+    if (!launch_tilt_sum(nullptr, npix, nt_out, T, partial.data(), out)) return -2;
+    return (int)rows;
+}
+
+int emu_div_vec(const float *in, const float *w, float d, size_t n, float *out)
+{
+    launch_div_vec(nullptr, in, w, d, n, out);
     return 0;
 }
 

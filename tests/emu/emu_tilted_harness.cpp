@@ -42,7 +42,7 @@ int emu_fbp_chain(int nt, size_t npix, const float *raw, const float *src, int n
         if (src_sum) {
             const size_t srows = tilt_sum_rows(npix);
             std::vector<float> sp(srows * (size_t)nt, kSentinel);
-            launch_tilt_sum(nullptr, npix, nt, TL, sp.data(), src_sum);
+            if (!launch_tilt_sum(nullptr, npix, nt, TL, sp.data(), src_sum)) return -2;
             for (float v : sp)
                 if (v == kSentinel) return -4;
         }

@@ -59,6 +59,8 @@ struct BlockSync {
 };
 inline BlockSync *g_sync = nullptr;
 
+// The block's threads are started once and walk the grid's blocks together (one block at a time, as before): a
+// grid of thousands of blocks costs two barrier rounds per block instead of `block` thread starts.
 template <class F>
 void run_grid(unsigned grid, unsigned block, size_t lds_bytes, F body)
 {
@@ -69,33 +71,41 @@ void run_grid(unsigned grid, unsigned block, size_t lds_bytes, F body)
     g_blockDim.x = block;
     g_gridDim.x = grid;
     const unsigned nwaves = block / 64;
-    for (unsigned b = 0; b < grid; ++b) {
-        BlockSync sync;
-        pthread_barrier_init(&sync.block, nullptr, block);
-        sync.waves.resize(nwaves);
-        for (auto &w : sync.waves) pthread_barrier_init(&w, nullptr, 64);
-        sync.slots.assign((size_t)block, 0.f);
-        g_sync = &sync;
-        void *raw = nullptr;
-        if (posix_memalign(&raw, 64, lds_bytes + 64) != 0) std::abort();
-        g_dyn_lds = (unsigned char *)raw;
-        std::memset(g_dyn_lds, 0xCD, lds_bytes + 64);
-        std::vector<std::thread> th;
-        th.reserve(block);
-        for (unsigned t = 0; t < block; ++t) {
-            th.emplace_back([&, t, b]() {
-                t_threadIdx.x = t;
+    BlockSync sync;
+    pthread_barrier_init(&sync.block, nullptr, block);
+    sync.waves.resize(nwaves);
+    for (auto &w : sync.waves) pthread_barrier_init(&w, nullptr, 64);
+    sync.slots.assign((size_t)block, 0.f);
+    g_sync = &sync;
+    void *raw = nullptr;
+    if (posix_memalign(&raw, 64, lds_bytes + 64) != 0) std::abort();
+    g_dyn_lds = (unsigned char *)raw;
+    std::memset(g_dyn_lds, 0xCD, lds_bytes + 64);
+    pthread_barrier_t next;  // between two blocks: every thread has left the body / the LDS is poisoned again
+    pthread_barrier_init(&next, nullptr, block);
+    std::vector<std::thread> th;
+    th.reserve(block);
+    for (unsigned t = 0; t < block; ++t) {
+        th.emplace_back([&, t]() {
+            t_threadIdx.x = t;
+            for (unsigned b = 0; b < grid; ++b) {
+                if (lds_bytes) {  // (a launch without dynamic LDS has nothing to poison: one barrier per block)
+                    if (t == 0) std::memset(g_dyn_lds, 0xCD, lds_bytes + 64);
+                    pthread_barrier_wait(&next);
+                }
                 t_blockIdx.x = b;
                 body();
-            });
-        }
-        for (auto &x : th) x.join();
-        std::free(raw);
-        g_dyn_lds = nullptr;
-        for (auto &w : sync.waves) pthread_barrier_destroy(&w);
-        pthread_barrier_destroy(&sync.block);
-        g_sync = nullptr;
+                pthread_barrier_wait(&next);
+            }
+        });
     }
+    for (auto &x : th) x.join();
+    pthread_barrier_destroy(&next);
+    std::free(raw);
+    g_dyn_lds = nullptr;
+    for (auto &w : sync.waves) pthread_barrier_destroy(&w);
+    pthread_barrier_destroy(&sync.block);
+    g_sync = nullptr;
 }
 
 }  // namespace thz_emu

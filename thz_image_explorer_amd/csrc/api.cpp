@@ -540,6 +540,8 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
         // ONE launch from the untilted cube: gather, multiplier and the wave rows of the sums (fft_fbp.hpp); the
         // re-laid traces' own sum is a small gather pass over the untilted cube (4 nt_in bytes per trace).
         // THZ_NO_FUSED_SUMS: developer knob as in thz_pipeline_ex, the sums as second passes for A/B measurements
+        if (src->d_src_sum && nt > (size_t)kTiltSumMaxNt)  // before anything is queued (no FBP plan is that long today)
+            return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: the source sum of a one-launch plan needs nt <= 2048");
         const size_t sum_rows = (io->d_sums && !getenv("THZ_NO_FUSED_SUMS")) ? pipeline_sum_rows(ctx->plan_d, npix, io->d_fd_cmask != nullptr) : 0;
         const size_t src_rows = src->d_src_sum ? tilt_sum_rows(npix) : 0;
         if (sum_rows || src_rows)
@@ -555,8 +557,9 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
         if (io->d_sums || src->d_src_sum) {
             StageTimer t(ctx, THZ_STAGE_MEAN);
             if (d_partial) launch_sum_rows_f64(ctx->stream, d_partial, sum_rows, 2 * nf, io->d_sums);
-            if (src->d_src_sum)
-                launch_tilt_sum(ctx->stream, npix, (int)nt, TL, reinterpret_cast<float *>(ctx->ws) + sum_rows * 2 * nf, src->d_src_sum);
+            if (src->d_src_sum &&
+                !launch_tilt_sum(ctx->stream, npix, (int)nt, TL, reinterpret_cast<float *>(ctx->ws) + sum_rows * 2 * nf, src->d_src_sum))
+                return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: the source sum of a one-launch plan needs nt <= 2048");
             if (int rc = check_launch(ctx)) return rc;
         }
         if (io->d_sums && !d_partial) {
@@ -655,31 +658,10 @@ int thz_pixel_sum(thz_ctx *ctx, size_t npix, size_t len, int ncomp, const float 
 int pixel_sum_rows(thz_ctx *ctx, const float *d_arr, const uint32_t *d_list, size_t npix, size_t L, float *d_out)
 {
     StageTimer t(ctx, d_list ? THZ_STAGE_ROI : THZ_STAGE_MEAN);
-    if (npix < 64) {
-        if (d_list) launch_gather_sum(ctx->stream, d_arr, L, d_list, (uint32_t)npix, 0.0f, d_out);
-        else launch_sum_axis0(ctx->stream, d_arr, npix, L, 0.0f, d_out);
-        return check_launch(ctx);
-    }
-    // two-level: row groups x column tiles with 4 rows of loads in flight per
-    // thread, then one small pass over the partial rows
-    const size_t max_groups = 2048, mid_groups = 32;
-    if (int rc = ensure_ws(ctx, (max_groups + mid_groups) * L * sizeof(float))) return rc;
-    float *part = reinterpret_cast<float *>(ctx->ws);
-    float *part2 = part + max_groups * L;
-    size_t groups = launch_colsum_partial(ctx->stream, d_arr, npix, L, part, max_groups, d_list);
-    if (groups == 0) {  // very long rows: plain strided sum
-        if (d_list) launch_gather_sum(ctx->stream, d_arr, L, d_list, (uint32_t)npix, 0.0f, d_out);
-        else launch_sum_axis0(ctx->stream, d_arr, npix, L, 0.0f, d_out);
-        return check_launch(ctx);
-    }
-    // the last level is one thread per column walking the partial rows one by one:
-    // keep it short (a 2048-row walk is 2048 dependent loads)
-    const float *src = part;
-    if (groups > 4 * mid_groups) {
-        groups = launch_colsum_partial(ctx->stream, part, groups, L, part2, mid_groups);
-        src = part2;
-    }
-    launch_sum_axis0(ctx->stream, src, groups, L, 0.0f, d_out);
+    const size_t ws_floats = pixel_sum_ws_floats(npix, L);
+    if (ws_floats)
+        if (int rc = ensure_ws(ctx, ws_floats * sizeof(float))) return rc;
+    launch_pixel_sum_rows(ctx->stream, d_arr, d_list, npix, L, reinterpret_cast<float *>(ctx->ws), d_out);
     return check_launch(ctx);
 }
 

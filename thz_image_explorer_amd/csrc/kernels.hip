@@ -600,11 +600,13 @@ __global__ __launch_bounds__(256) void k_intensity(size_t npix, int nt, float *_
         wave_sync();  // every lane has read x[0] before lane 0 overwrites it
         float acc = 0.0f;
         if constexpr (VEC) {
+            // (16-byte accesses that promise 4-byte alignment only: a trace's image is the same bits wherever `data` starts)
             for (int e = 4 * lane; e < nt; e += 4 * kWave) {
-                float4 v = *reinterpret_cast<const float4 *>(x + e);
+                float4 v;
+                load_f4(x + e, v.x, v.y, v.z, v.w);
                 if (subtract_bias) {
                     v = make_float4(v.x - off, v.y - off, v.z - off, v.w - off);
-                    *reinterpret_cast<float4 *>(x + e) = v;
+                    store_f4(x + e, v.x, v.y, v.z, v.w);
                 }
                 acc += v.x * v.x;
                 acc += v.y * v.y;
@@ -3031,14 +3033,16 @@ size_t tilt_sum_rows(size_t npix)
     return g < 1 ? 1 : g;
 }
 
-void launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out)
+bool launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out)
 {
+    if (nt_out < 1 || nt_out > kTiltSumMaxNt) return false;  // k_tilt_sum<8> covers 8 x 256 samples and no more
     const size_t rows = tilt_sum_rows(npix);
     if (nt_out <= 5 * 256)  // every length of an FBP plan
         THZ_LAUNCH(k_tilt_sum<5>, (unsigned)rows, 256, 0, st, npix, tilt.nt_in, nt_out, tilt.src, tilt.taper, tilt.ins, partial);
     else
         THZ_LAUNCH(k_tilt_sum<8>, (unsigned)rows, 256, 0, st, npix, tilt.nt_in, nt_out, tilt.src, tilt.taper, tilt.ins, partial);
     launch_sum_rows_f64(st, partial, rows, (size_t)nt_out, out);
+    return true;
 }
 
 void launch_fd_mask(hipStream_t st, size_t npix, int nf, c32 *fft, float *amp, const float *mask)
@@ -3090,7 +3094,7 @@ void launch_intensity(hipStream_t st, size_t npix, int nt, float *data, float *i
                       int subtract_bias)
 {
     const unsigned grid = grid_1d(npix * kWave, 256, kNumCU * 8);
-    if (nt % 4 == 0 && (uintptr_t)data % 16 == 0)
+    if (nt % 4 == 0)
         THZ_LAUNCH(k_intensity<true>, grid, 256, 0, st, npix, nt, data, img, subtract_bias);
     else
         THZ_LAUNCH(k_intensity<false>, grid, 256, 0, st, npix, nt, data, img, subtract_bias);
@@ -3107,25 +3111,65 @@ void launch_sum_rows_f64(hipStream_t st, const float *arr, size_t n0, size_t inn
     THZ_LAUNCH(k_sum_rows_f64, grid_1d(inner, 256, kNumCU * 16), 256, 0, st, arr, n0, inner, out);
 }
 
+// the KC of k_colsum_partial<KC> for rows of L floats (0: too wide for the kernel)
+int colsum_partial_kc(size_t L)
+{
+    const size_t chunks = (L / 4 + 255) / 256;  // 16-byte chunks per thread
+    return chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 3 ? 3 : chunks <= 5 ? 5 : chunks <= 8 ? 8 : 0;
+}
+
 // returns the number of partial rows written to `partial` (each L floats); 0 if L is
 // too wide for the kernel (caller falls back)
 size_t launch_colsum_partial(hipStream_t st, const float *arr, size_t nrows, size_t L,
                              float *partial, size_t max_groups, const uint32_t *list)
 {
-    const size_t chunks = (L / 4 + 255) / 256;  // 16-byte chunks per thread
-    if (chunks > 8) return 0;
+    const int kc = colsum_partial_kc(L);
+    if (kc == 0) return 0;
     size_t groups = (size_t)kNumCU * 8;
     if (groups > max_groups) groups = max_groups;
     if (groups > nrows) groups = nrows;
     if (groups < 1) groups = 1;
     const size_t rows_per_group = (nrows + groups - 1) / groups;
     groups = (nrows + rows_per_group - 1) / rows_per_group;
-    if (chunks <= 1) THZ_LAUNCH((k_colsum_partial<1>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
-    else if (chunks <= 2) THZ_LAUNCH((k_colsum_partial<2>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
-    else if (chunks <= 3) THZ_LAUNCH((k_colsum_partial<3>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
-    else if (chunks <= 5) THZ_LAUNCH((k_colsum_partial<5>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
+    if (kc == 1) THZ_LAUNCH((k_colsum_partial<1>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
+    else if (kc == 2) THZ_LAUNCH((k_colsum_partial<2>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
+    else if (kc == 3) THZ_LAUNCH((k_colsum_partial<3>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
+    else if (kc == 5) THZ_LAUNCH((k_colsum_partial<5>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
     else THZ_LAUNCH((k_colsum_partial<8>), (unsigned)groups, 256, 0, st, arr, nrows, L, rows_per_group, partial, list);
     return groups;
+}
+
+// Σ over the rows list[0 .. nrows) of arr (list null: rows 0 .. nrows - 1), rows of L floats; order-free (parallel)
+// sums — the pixel sums behind the fast means and, with a list, a region of interest's.  `ws`: pixel_sum_ws_floats()
+// floats of scratch (none below 64 rows).
+constexpr size_t kPixelSumMaxGroups = 2048, kPixelSumMidGroups = 32;
+
+size_t pixel_sum_ws_floats(size_t nrows, size_t L)
+{
+    return nrows < 64 ? 0 : (kPixelSumMaxGroups + kPixelSumMidGroups) * L;
+}
+
+void launch_pixel_sum_rows(hipStream_t st, const float *arr, const uint32_t *list, size_t nrows, size_t L, float *ws, float *out)
+{
+    auto ordered = [&]() {  // one thread per column walking the rows one by one
+        if (list) launch_gather_sum(st, arr, L, list, (uint32_t)nrows, 0.0f, out);
+        else launch_sum_axis0(st, arr, nrows, L, 0.0f, out);
+    };
+    if (nrows < 64) return ordered();
+    // two-level: row groups x column tiles with 4 rows of loads in flight per
+    // thread, then one small pass over the partial rows
+    float *part = ws;
+    float *part2 = part + kPixelSumMaxGroups * L;
+    size_t groups = launch_colsum_partial(st, arr, nrows, L, part, kPixelSumMaxGroups, list);
+    if (groups == 0) return ordered();  // very long rows: plain strided sum
+    // the last level is one thread per column walking the partial rows one by one:
+    // keep it short (a 2048-row walk is 2048 dependent loads)
+    const float *src = part;
+    if (groups > 4 * kPixelSumMidGroups) {
+        groups = launch_colsum_partial(st, part, groups, L, part2, kPixelSumMidGroups);
+        src = part2;
+    }
+    launch_sum_axis0(st, src, groups, L, 0.0f, out);
 }
 
 void launch_roi_mask(hipStream_t st, const uint64_t *d_poly, int n, uint64_t x_min, uint64_t x_max,

@@ -162,9 +162,11 @@ bool launch_pipeline_tilted(hipStream_t st, const PlanDev &P, size_t npix, const
                             const float *mask, const float *post_win, c32 *fft_out, float *amp_out, float *ph_out,
                             float *data_out, float *img, const c32 *cmask, float *sum_partial);
 // out[n] = sum over the pixels of the re-laid (tilted, tapered) samples, n < nt_out: tilt_sum_rows(npix) partial rows
-// of nt_out floats (sequential f32 per row), added in double
+// of nt_out floats (sequential f32 per row), added in double.  nt_out <= kTiltSumMaxNt (a thread holds one sample per
+// 256 of the axis in registers); false, and nothing launched, for a longer axis
+constexpr int kTiltSumMaxNt = 2048;
 size_t tilt_sum_rows(size_t npix);
-void launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out);
+bool launch_tilt_sum(hipStream_t st, size_t npix, int nt_out, const FBPTilt &tilt, float *partial, float *out);
 void launch_fd_mask(hipStream_t st, size_t npix, int nf, c32 *fft, float *amp, const float *mask);
 void launch_fd_cmask(hipStream_t st, size_t npix, int nf, int nt, c32 *fft, float *amp,
                      const c32 *cmask);
@@ -185,6 +187,13 @@ void launch_sum_rows_f64(hipStream_t st, const float *arr, size_t n0, size_t inn
 // list (or null): add arr's rows list[0 .. nrows) instead of rows 0 .. nrows - 1 (a region of interest's pixels)
 size_t launch_colsum_partial(hipStream_t st, const float *arr, size_t nrows, size_t L,
                              float *partial, size_t max_groups, const uint32_t *list = nullptr);
+// the k_colsum_partial<KC> that launch_colsum_partial runs for rows of L floats: 1, 2, 3, 5 or 8; 0 where it refuses
+int colsum_partial_kc(size_t L);
+// column sums of arr's rows (of the rows list[0 .. nrows) with a list), order-free: the ordered walk below 64 rows and
+// for rows too long for launch_colsum_partial, else one or two levels of partial rows in `ws`
+// (pixel_sum_ws_floats(nrows, L) floats) and a last ordered walk over those
+size_t pixel_sum_ws_floats(size_t nrows, size_t L);
+void launch_pixel_sum_rows(hipStream_t st, const float *arr, const uint32_t *list, size_t nrows, size_t L, float *ws, float *out);
 void launch_roi_mask(hipStream_t st, const uint64_t *d_poly, int n, uint64_t x_min, uint64_t x_max,
                      uint64_t y_min, uint64_t y_max, uint64_t x_size, uint64_t y_size,
                      uint8_t *d_mask);
