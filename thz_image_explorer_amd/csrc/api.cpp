@@ -490,7 +490,8 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
     // Pixel sums: inside the launch where the plan's fused kernel can (the F kernels, nt = 1024 / 2048 / 4096: the
     // block's waves add their amplitudes and unwrapped phases to one set of accumulators in LDS, group by group in
     // ticket order — fft_f.hpp, FSums — and a small pass adds the blocks' rows: 15.4 against 17.8 ms per Mi traces of
-    // 4096 samples, profiles/r02_sums_in_kernel.txt), otherwise as a second pass over the two arrays just written
+    // 4096 samples, profiles/r02_sums_in_kernel.txt; the P, PH and FBP kernels likewise: pipeline_sum_rows says how many
+    // rows a plan's launch leaves), otherwise as a second pass over the two arrays just written
     // (8 nf bytes per trace).  THZ_NO_FUSED_SUMS: developer knob, forces the second pass for A/B measurements.
     const size_t sum_rows = (io->d_sums && !getenv("THZ_NO_FUSED_SUMS"))
                                 ? pipeline_sum_rows(ctx->plan_d, npix, io->d_fd_cmask != nullptr, band_lo4, band_n) : 0;

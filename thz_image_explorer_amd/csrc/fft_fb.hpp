@@ -32,8 +32,8 @@ struct FBArgs {
     float *img;             // npix or nullptr
     const cx *w;            // nt: exp(-i pi n^2 / nt)
     const cx *bf;           // M : FFT_M(b) / M
-    const cx *cmask;        // nf complex multipliers on top of `mask`, or nullptr (P kernels)
-    float *sum_partial;     // (gridDim.x, 2 nf): every block's sums of its traces' stored amplitudes | unwrapped phases (k_p<..., SUMS>)
+    const cx *cmask;        // nf complex multipliers on top of `mask`, or nullptr (P, PH and FBP kernels)
+    float *sum_partial;     // (gridDim.x, 2 nf): every block's sums of its traces' stored amplitudes | unwrapped phases (k_p / k_ph<..., SUMS>)
     const float *pre_win2;  // nt or nullptr: a second window behind pre_win (k_fbp<kFwd>, fft_fbp.hpp)
 };
 

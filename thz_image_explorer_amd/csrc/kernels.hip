@@ -2598,32 +2598,67 @@ static void dispatch_p(hipStream_t st, const PlanDev &P, FBArgs &A)
 }
 
 // PH kernels (fft_ph.hpp): even lengths whose half is a P plan
-template <class PL, int MODE>
+template <class PL>
+static size_t ph_grid(size_t npix, bool sums)
+{
+    const unsigned waves = (unsigned)PHLayout<PL>::waves(sums);
+    size_t g = (npix + waves - 1) / waves;
+    if (g > (size_t)kNumCU) g = kNumCU;
+    if (g_grid_cap_override > 0 && g > (size_t)g_grid_cap_override) g = (size_t)g_grid_cap_override;
+    if (g < 1) g = 1;
+    return g;
+}
+
+template <class PL, int MODE, bool CM = false, bool SUMS = false>
 static void launch_ph(hipStream_t st, const PlanDev &P, FBArgs &A)
 {
     A.nt = P.nt;
     A.nf = P.nf;
-    const unsigned waves = (unsigned)PHLayout<PL>::waves();
-    size_t g = (A.npix + waves - 1) / waves;
-    if (g > (size_t)kNumCU) g = kNumCU;
-    if (g_grid_cap_override > 0 && g > (size_t)g_grid_cap_override) g = (size_t)g_grid_cap_override;
-    if (g < 1) g = 1;
-    const size_t lds = PHLayout<PL>::lds_bytes((int)waves);
+    const unsigned waves = (unsigned)PHLayout<PL>::waves(SUMS);
+    const size_t g = ph_grid<PL>(A.npix, SUMS);
+    const size_t lds = PHLayout<PL>::lds_bytes((int)waves, SUMS);
     PHTables T{reinterpret_cast<const cx *>(P.p_t1), reinterpret_cast<const cx *>(P.p_t2),
                reinterpret_cast<const cx *>(P.p_t2) + PL::T2_ENTRIES};
-    allow_dynamic_lds(k_ph<PL, MODE>, lds);
-    THZ_LAUNCH((k_ph<PL, MODE>), (unsigned)g, waves * kWave, lds, st, A, T);
+    allow_dynamic_lds(k_ph<PL, MODE, CM, SUMS>, lds);
+    THZ_LAUNCH((k_ph<PL, MODE, CM, SUMS>), (unsigned)g, waves * kWave, lds, st, A, T);
+}
+
+// the fused chain picks its compile-time extras: A.cmask -> CM, A.sum_partial -> SUMS
+template <class PL, int MODE>
+static void launch_ph_variant(hipStream_t st, const PlanDev &P, FBArgs &A)
+{
+    if constexpr (MODE == kPipe) {
+        const int sel = (A.cmask ? 1 : 0) | (A.sum_partial ? 2 : 0);
+        if (sel == 3) launch_ph<PL, MODE, true, true>(st, P, A);
+        else if (sel == 2) launch_ph<PL, MODE, false, true>(st, P, A);
+        else if (sel == 1) launch_ph<PL, MODE, true, false>(st, P, A);
+        else launch_ph<PL, MODE>(st, P, A);
+    } else {
+        launch_ph<PL, MODE>(st, P, A);
+    }
 }
 
 template <int MODE>
 static void dispatch_ph(hipStream_t st, const PlanDev &P, FBArgs &A)
 {
     switch (P.half_n) {
-    case 1001: launch_ph<PPlan1001, MODE>(st, P, A); break;
-    case 1200: launch_ph<PPlan1200, MODE>(st, P, A); break;
-    case 1500: launch_ph<PPlan1500, MODE>(st, P, A); break;
-    case 2000: launch_ph<PPlan2000, MODE>(st, P, A); break;
-    default: launch_ph<PPlan1000, MODE>(st, P, A); break;
+    case 1001: launch_ph_variant<PPlan1001, MODE>(st, P, A); break;
+    case 1200: launch_ph_variant<PPlan1200, MODE>(st, P, A); break;
+    case 1500: launch_ph_variant<PPlan1500, MODE>(st, P, A); break;
+    case 2000: launch_ph_variant<PPlan2000, MODE>(st, P, A); break;
+    default: launch_ph_variant<PPlan1000, MODE>(st, P, A); break;
+    }
+}
+
+// rows of the partial-sum workspace of a PH launch with in-launch sums: one per block
+static size_t ph_sum_rows(const PlanDev &P, size_t npix)
+{
+    switch (P.half_n) {
+    case 1001: return ph_grid<PPlan1001>(npix, true);
+    case 1200: return ph_grid<PPlan1200>(npix, true);
+    case 1500: return ph_grid<PPlan1500>(npix, true);
+    case 2000: return ph_grid<PPlan2000>(npix, true);
+    default: return ph_grid<PPlan1000>(npix, true);
     }
 }
 
@@ -2910,6 +2945,8 @@ size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4
         if (P.conv_m == FBPPlan2304::N) return fbp_grid<FBPPlan2304>(npix) * (size_t)FBPLayout<FBPPlan2304>::waves();
         return fbp_grid<FBPPlan2560>(npix) * (size_t)FBPLayout<FBPPlan2560>::waves();
     }
+    if ((P.family == kFamilyFB2 || P.family == kFamilyFB4 || P.family == kFamilyFB8) && P.half_n)
+        return ph_sum_rows(P, npix);  // one row per block (fft_ph.hpp, PHSums), with or without a multiplier
     if (P.family != kFamilyF) return 0;
     switch (P.nt) {
     case 4096: return f_sum_rows<FPlan4096>(npix, cmask, cmask && f_band_fits(P, band_lo4, band_n));
@@ -2941,17 +2978,20 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
         dispatch_f<kPipe>(st, P, A, true);
         return;
     }
-    if (cmask && !((P.family == kFamilyP || P.family == kFamilyFBP) && fft_out && amp_out && ph_out && data_out)) {
+    const bool ph_plan = (P.family == kFamilyFB2 || P.family == kFamilyFB4 || P.family == kFamilyFB8) && P.half_n;
+    if (cmask && !((P.family == kFamilyP || P.family == kFamilyFBP || ph_plan) && fft_out && amp_out && ph_out && data_out)) {
         // every other family: the complex multiply is its own pass over the stored spectrum
         launch_fft_fwd(st, P, npix, raw, pre_win, nullptr, nullptr, fft_out, amp_out, ph_out, mask, cmask);
         launch_fft_inv(st, P, npix, fft_out, post_win, data_out, img);
         return;
     }
-    if ((P.family == kFamilyFB2 || P.family == kFamilyFB4 || P.family == kFamilyFB8) && P.half_n && fft_out && amp_out && ph_out && data_out) {
+    if (ph_plan && fft_out && amp_out && ph_out && data_out) {
         FBArgs A{};  // one launch: half-length transform, split, epilogue, merge, inverse (fft_ph.hpp)
         A.npix = npix; A.in = raw; A.pre_win = pre_win; A.mask = mask ? mask : P.ones;
         A.post_win = post_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out; A.ph_out = ph_out;
         A.data_out = data_out; A.img = img;
+        A.cmask = reinterpret_cast<const cx *>(cmask);
+        A.sum_partial = sum_partial;  // pipeline_sum_rows(P, npix, cmask) rows, or null
         dispatch_ph<kPipe>(st, P, A);
         return;
     }

@@ -135,7 +135,7 @@ void launch_fft_fwd(hipStream_t st, const PlanDev &P, size_t npix, const float *
 void launch_fft_inv(hipStream_t st, const PlanDev &P, size_t npix, const c32 *fft_in,
                     const float *win, float *out, float *img);
 // sum_partial: pipeline_sum_rows(P, npix, cmask != nullptr) rows of 2 nf floats, or null — every block's sums of the
-// stored amplitudes | unwrapped phases of its traces (the F kernels' kCfgSums, fft_f.hpp); a second small launch
+// stored amplitudes | unwrapped phases of its traces (the F kernels' kCfgSums, fft_f.hpp; PSums / PHSums of the P and PH kernels; one row per wave from the FBP kernels); a second small launch
 // (launch_sum_axis0 over the rows) makes the pixel sums of them
 // band_lo4 / band_n (multiples of 4; 0, 0 = unknown): the bins outside [band_lo4, band_lo4 + band_n) are zero in `mask` —
 // lets the nt = 4096 chain with a complex multiplier and the sums stage a band-limited table (fft_f.hpp, kCfgBand)
