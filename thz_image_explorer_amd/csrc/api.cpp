@@ -466,6 +466,9 @@ int thz_pipeline_ex(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io)
 // the band's first and last bin back): every bin outside [band_lo, band_hi) is zero in io->d_fd_mask.  With a complex
 // multiplier the nt = 4096 kernel then stages only the band's bins (fft_f.hpp, kCfgBand).  0, 0: unknown.
 // keep: the bins of d_fft / d_amp the launch must store (ctx.hpp, KeepRange); null: every bin, as thz_pipeline_ex.
+// A caller that passes a range of its own there has checked the multiplier vector: exactly zero outside the band, a
+// complex multiplier finite there.  The launch may then leave out the inverse transform's products with those zeros
+// (fft_f.hpp, "band pruning"); one that writes every bin computes every bin.
 int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi, KeepRange *keep)
 {
     if (keep) keep->honoured = false;
@@ -476,7 +479,7 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
         keep_n = (int)(((keep->hi + 3) & ~(size_t)3) - (size_t)keep_lo4);
     }
     int band_lo4 = 0, band_n = 0;
-    if (band_hi > band_lo && io && io->d_fd_cmask) {
+    if (band_hi > band_lo && io) {
         band_lo4 = (int)(band_lo & ~(size_t)3);
         band_n = (int)(((band_hi + 3) & ~(size_t)3) - (size_t)band_lo4);
     }

@@ -176,6 +176,9 @@ enum : int {
     kCfgBar = 8,       // the block's waves meet at a barrier before each store phase (FArgs::bar says which)
     kCfgKeep = 32,     // fused chain: spectrum and amplitude stores obey FArgs' keep range (built beside the plain form: the
                        // range-checked buffer stores cost a launch that writes everything 1.5-2.6 %, so it runs the plain one)
+    kCfgLow = 64,      // with kCfgKeep: the multiplier is zero from bin N/2 + M1 on and the keep range ends there at the
+                       // latest — f_inverse_input leaves out the half-terms that are products with those zeros ("band
+                       // pruning" below)
     kCfgBand = 16      // with kCfgCMask: the staged multiplier table covers only the bins FArgs::band_lo4 .. + band_n — where
                        // the real band pass is not zero — between two quads of zeros that every other bin's index is clamped
                        // to.  Half the table at the default 0.2-5 THz: what lets the nt = 4096 chain with the complex
@@ -516,13 +519,17 @@ __device__ __forceinline__ void r2c_pair(cx a, cx b, cx w2, cx &xk, cx &xn)
 // unconjugated) and wc = conj(w2):  Z' = E + i (D conj(w)) = E + 2 D wc  with E = {p.x, m.y},
 // D = {m.x, p.y}, p = X[k] + X[N-k], m = X[k] - X[N-k].  Same idea as r2c_pair: no conjugate is ever
 // built, and the two FMAs write the exchanged pair directly.
-__device__ __forceinline__ cx c2r_swapped(cx xk, cx xn, cx wc)
+__device__ __forceinline__ cx c2r_swapped_pm(cx p, cx m, cx wc)
 {
-    const cx p = xk + xn, m = xk - xn;
     const cx bs = {-wc.y, wc.x};
     const cx t = m.xx * wc + p.yy * bs;  // D * wc
     return cx{fmaf(2.0f, t.y, m.y), fmaf(2.0f, t.x, p.x)};
 }
+__device__ __forceinline__ cx c2r_swapped(cx xk, cx xn, cx wc) { return c2r_swapped_pm(xk + xn, xk - xn, wc); }
+// One-term forms: the other term is a product with a zero of the multiplier (kCfgLow).  x + (+-0) and x - (+-0) are x
+// wherever x is not itself a zero, so these give c2r_swapped's bits up to the sign of an exact zero.
+__device__ __forceinline__ cx c2r_swapped_fwd(cx xk, cx wc) { return c2r_swapped_pm(xk, xk, wc); }   // X[N-k] H[N-k] = 0
+__device__ __forceinline__ cx c2r_swapped_mir(cx xn, cx wc) { return c2r_swapped_pm(xn, -xn, wc); }  // X[k] H[k] = 0
 
 }  // namespace thz
 
@@ -570,6 +577,18 @@ __device__ __forceinline__ void load_f4(const float *p, float &a, float &b, floa
 // NOT covered: a finite trace whose transform overflows to Inf in some bins only, none of them among the first 256 —
 // a full write stores NaN (Inf * 0) at those bins where they are out of band, a launch with a keep range leaves the
 // earlier value.  (Samples of 1e30 and more; the time trace of such a pixel is NaN either way.)
+// Band pruning.  A launch with a keep range that is also given the band [band_lo4, band_lo4 + band_n) carries its
+// caller's promise that the multiplier is exactly zero at every bin outside it (a complex one: finite times that zero) —
+// what the session checks on the vector before it passes a keep range at all.  Where band and keep range both end at
+// or below bin N/2 + M1 such a launch runs the kCfgLow build, which leaves out of the inverse transform's input the
+// products with those zeros, trace by trace for the finite ones (a non-finite trace, found by the keep range's ballot,
+// is computed in full): dropped at compile time are the forward half-term of f_inverse_input for j1 >= R1/2 + 1 — with
+// its 1 KiB spectrum store, which the window would drop — and the mirror half-term for j1 <= R1/2 - 2.
+// Spectrum, amplitudes, phases, sums and image are the unpruned launch's bits.  The time trace can differ in the sign
+// of an exact zero: the unpruned form adds X[k] H[k] and a product +-0, the pruned one takes X[k] H[k], and the two
+// differ only where that value is itself a zero (so a multiplier of -0 outside the band is as good as +0).
+// band_n == 0: nothing is known, nothing is pruned.  (The spectrum epilogue computes every group: skipping the
+// multiplier, products and square roots of the groups wholly outside the band was tried and measured no gain.)
 constexpr int kFKeepAll = 1 << 30;
 
 // A window of an output row whose stores carry a per-lane predicate at no cost in control flow or registers: the
@@ -632,7 +651,8 @@ struct FArgs {
     float *data_out;        // (npix, nt) final trace            [inv, pipeline]
     float *img;             // (npix) or null
     int band_lo4, band_n;   // kCfgBand: first bin (a multiple of 4) and number of bins (a multiple of 4, <= P::BAND_BINS) of
-                            // the staged complex multiplier; the real mask is zero at every bin outside
+                            // the staged complex multiplier; the real mask is zero at every bin outside.  kCfgKeep: the
+                            // multiplier is zero outside these bins ("band pruning"); band_n == 0: unknown
     float *sum_partial;     // (gridDim.x, 2 nf): every block's sums of its traces' stored amplitudes | unwrapped
                             // phases, written whole by the block (zeros if it had no trace); kCfgSums only
     int keep_lo4 = 0, keep_n = kFKeepAll;  // fused chain: the launch must store spectrum and amplitudes of the bins
@@ -1104,7 +1124,11 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
 // STORE (fused chain, with MASKED): fft_row = the trace's row of the spectrum output; the masked bins n < N — the
 // values the inverse transform is built from, to the bit — are stored from here (bin N: the spectrum epilogue), those
 // of the bins [keep_lo, keep_lo + keep_n) only (FArgs' keep range, as f_spectrum_epilogue hands it on).
-template <class P, bool MASKED, bool CMASK = false, bool WC = false, bool STORE = false, bool BAND = false, bool KEEP = false>
+// LOW (kCfgLow, with KEEP): the multiplier is zero at every bin >= N/2 + M1 and the keep range ends there at the
+// latest.  X[n] H[n] is then a zero for j1 >= R1/2 + 1 and X[N-n] H[N-n] for j1 <= R1/2 - 2: those half-terms — two
+// LDS reads, the multiply, the split's adds, the spectrum store of the former — are left out at compile time.
+template <class P, bool MASKED, bool CMASK = false, bool WC = false, bool STORE = false, bool BAND = false, bool KEEP = false,
+          bool LOW = false>
 __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, const cx *wg_s,
                                                 const float *__restrict__ mask, int lane,
                                                 cx (&r)[P::C1][P::R1], cx *fft_row = nullptr, int band_off = 0, int band_cap = 0,
@@ -1114,6 +1138,7 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
     // (the stand-alone inverse must land on the same samples from the stored spectrum, bit for bit)
 #pragma clang fp contract(off)
     static_assert(!STORE || MASKED, "the stored spectrum is the masked one");
+    static_assert(!LOW || (KEEP && STORE), "the pruned form is the fused chain's with a keep range");
     constexpr int N = P::N, R1 = P::R1, C1 = P::C1, M1 = P::M1;
     cx wlc[C1];  // conj of the lane's staged twiddles: the product below is conj(w2) directly
     if constexpr (WC) {
@@ -1152,13 +1177,15 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
 #pragma unroll
     for (int j1 = 0; j1 < R1; ++j1) {
         const cx wgc = cx_conj(wg_s[j1]);  // conj(w2n[M1 j1]), wave-uniform
+        const bool has_f = !LOW || j1 <= R1 / 2, has_m = !LOW || j1 >= R1 / 2 - 1;  // (compile-time: j1 is unrolled)
         cx kept[C1];
 #pragma unroll
         for (int c = 0; c < C1; ++c) {
             const int off = M1 * j1 + c;
             const cx wc = j1 == 0 ? wlc[c] : cx_mul(wlc[c], wgc);
-            cx xk = buf[fbase[j1 & 1][c] + M1 * j1];
-            cx xn = buf[mbase[j1 & 1][c] - M1 * j1];
+            cx xk = cx{0.0f, 0.0f}, xn = cx{0.0f, 0.0f};
+            if (has_f) xk = buf[fbase[j1 & 1][c] + M1 * j1];
+            if (has_m) xn = buf[mbase[j1 & 1][c] - M1 * j1];
             if (off == 0 && !(MASKED && CMASK)) {
                 // n == 0 only in lane 0: X[0] and X[N] are real (realfft ignores /
                 // rejects their imaginary parts, SURVEY a'-4)
@@ -1170,30 +1197,32 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
             if constexpr (MASKED && CMASK) {
                 const cx *hm = reinterpret_cast<const cx *>(mask);
                 if constexpr (BAND) {
-                    xk = cx_mul_pk(xk, hm[f_band_index(mk_f + band_off + off, band_cap)]);
-                    xn = cx_mul_pk(xn, hm[f_band_index(mk_r + band_off + (TOP - off), band_cap)]);
+                    if (has_f) xk = cx_mul_pk(xk, hm[f_band_index(mk_f + band_off + off, band_cap)]);
+                    if (has_m) xn = cx_mul_pk(xn, hm[f_band_index(mk_r + band_off + (TOP - off), band_cap)]);
                 } else {
-                    xk = cx_mul_pk(xk, hm[mk_f + off]);
-                    xn = cx_mul_pk(xn, hm[mk_r + (TOP - off)]);
+                    if (has_f) xk = cx_mul_pk(xk, hm[mk_f + off]);
+                    if (has_m) xn = cx_mul_pk(xn, hm[mk_r + (TOP - off)]);
                 }
                 if (off == 0 && lane == 0) {
                     xk.y = 0.0f;
                     xn.y = 0.0f;
                 }
             } else if constexpr (MASKED) {
-                const float mk = mask[mk_f + off], mn = mask[mk_r + (TOP - off)];
-                xk = cx{xk.x * mk, xk.y * mk};
-                xn = cx{xn.x * mn, xn.y * mn};
+                const float mk = has_f ? mask[mk_f + off] : 0.0f, mn = has_m ? mask[mk_r + (TOP - off)] : 0.0f;
+                if (has_f) xk = cx{xk.x * mk, xk.y * mk};
+                if (has_m) xn = cx{xn.x * mn, xn.y * mn};
             }
             kept[c] = xk;
-            r[c][j1] = c2r_swapped(xk, xn, wc);
+            r[c][j1] = !has_m ? c2r_swapped_fwd(xk, wc) : !has_f ? c2r_swapped_mir(xn, wc) : c2r_swapped(xk, xn, wc);
         }
         if constexpr (STORE) {
             // bins M1 j1 + C1 lane (+ 1), 8 bytes each; the offset is formed here, not sixteen of them up front
             if constexpr (KEEP) {
-                const unsigned at = (unsigned)launder_after(rel + 8 * M1 * j1, kept[0].x);
-                if constexpr (C1 == 2) row_store_f4(frow, at, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
-                else row_store_f2(frow, at, kept[0].x, kept[0].y);
+                if (has_f) {  // LOW: the others lie behind the keep range
+                    const unsigned at = (unsigned)launder_after(rel + 8 * M1 * j1, kept[0].x);
+                    if constexpr (C1 == 2) row_store_f4(frow, at, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
+                    else row_store_f2(frow, at, kept[0].x, kept[0].y);
+                }
             } else {
                 if constexpr (C1 == 2) store_f4(frow_all + 2 * M1 * j1, kept[0].x, kept[0].y, kept[1].x, kept[1].y);
                 else *reinterpret_cast<float2 *>(frow_all + 2 * M1 * j1) = make_float2(kept[0].x, kept[0].y);
@@ -1315,9 +1344,11 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     constexpr bool SUMS = (CFG & kCfgSums) != 0;
     constexpr bool BAND = (CFG & kCfgBand) != 0 && CMASK;
     constexpr bool KEEP = (CFG & kCfgKeep) != 0;
+    constexpr bool LOW = (CFG & kCfgLow) != 0;
     static_assert(!KEEP || MODE == kPipe, "the keep range is the fused chain's");
+    static_assert(!LOW || KEEP, "the pruned inverse input needs the keep range");
     static_assert(!SUMS || (MODE == kPipe && AMP_PHASE && (CFG & kCfgBar) != 0), "sums: fused chain, block-uniform trace loop");
-    constexpr int ME = P::mask_entries(CFG & ~kCfgKeep);
+    constexpr int ME = P::mask_entries(CFG & ~(kCfgKeep | kCfgLow));
     const int nf = N + 1;
     const int lane = lane_id();
     const int wib = THZ_UNIFORM((int)(threadIdx.x >> 6));
@@ -1528,11 +1559,27 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
                 buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, p, A, lane, &sums, &keep_lo, &keep_n);
             if constexpr (MODE == kPipe) {
                 cx r[C1][R1];
-                f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
-                                                                mask_l, lane, r, A.fft_out + p * nf, 4 - A.band_lo4, A.band_n + 4,
-                                                                THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
-                wave_sync();  // every lane has read Z before the core overwrites buf
-                f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+                if constexpr (LOW) {
+                    // a non-finite trace (the epilogue's ballot widened its range to every bin) is not pruned either.  The
+                    // wave-uniform branch takes pass 1 with it, so that r is dead where the two paths join: joined behind
+                    // f_inverse_input alone the kCfgLow builds spill 12-18 VGPRs, with the prefetch and passes 2-3 inside
+                    // as well 38-43.
+                    auto inverse = [&](auto low_tag) {
+                        f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP, decltype(low_tag)::value>(
+                            buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, lane, r, A.fft_out + p * nf,
+                            4 - A.band_lo4, A.band_n + 4, THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
+                        wave_sync();  // every lane has read Z before the core overwrites buf
+                        f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+                    };
+                    if (THZ_UNIFORM(keep_n) == kFKeepAll) inverse(FFalse{});
+                    else inverse(FTrue{});
+                } else {
+                    f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
+                                                                    mask_l, lane, r, A.fft_out + p * nf, 4 - A.band_lo4, A.band_n + 4,
+                                                                    THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
+                    wave_sync();  // every lane has read Z before the core overwrites buf
+                    f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+                }
                 if (p + stride < A.npix) f_load_raw<P>(A.in + (p + stride) * NT, lane, raw);
                 f_core_pass23<P>(buf, t2, ad, lane);
             }

@@ -2390,9 +2390,16 @@ static size_t f_grid(size_t npix)
     return g;
 }
 
+#ifdef THZ_EMU
+thread_local int g_f_last_cfg = -1;  // tests (the emulation harness): the kCfg bits of this thread's latest k_f launch
+#endif
+
 template <class PL, int MODE, int CFG>
 static void launch_f(hipStream_t st, const PlanDev &P, const FArgs &A)
 {
+#ifdef THZ_EMU
+    g_f_last_cfg = CFG;
+#endif
     const unsigned kBlock = f_block_threads<PL, CFG>();
     const size_t lds = PL::lds_bytes((int)(kBlock / kWave), CFG);
     const size_t g = f_grid<PL, MODE, CFG>(A.npix);
@@ -2421,6 +2428,22 @@ static bool f_band_fits(const PlanDev &P, int lo4, int n)
     return P.nt == 4096 && n > 0 && n <= FPlan4096::BAND_BINS && lo4 >= 0 && lo4 % 4 == 0 && n % 4 == 0;
 }
 
+// the kCfgLow builds (fft_f.hpp, "band pruning"): nt = 4096 with the store barriers, for a launch whose band — outside
+// which its caller promises the multiplier to be zero — and keep range both end at or below bin N/2 + M1.
+// A complex multiplier with the sums has its kCfgLow build on the band-limited table only: a band that ends below
+// N/2 + M1 but is wider than BAND_BINS (say bins 0 .. 1100) runs the kCfgKeep build on the full table.
+// THZ_F_LOW=0: developer knob, such a launch runs the kCfgKeep build instead (A/B measurements).
+static bool f_low_fits(const PlanDev &P, const FArgs &A)
+{
+    constexpr int kTop = FPlan4096::N / 2 + FPlan4096::M1;
+    if (P.nt != 4096 || A.band_n <= 0 || A.band_lo4 < 0 || A.band_lo4 + A.band_n > kTop) return false;
+    if (A.keep_n >= kFKeepAll || A.keep_lo4 + A.keep_n > kTop) return false;
+#ifndef THZ_EMU
+    if (const char *e = getenv("THZ_F_LOW")) return atoi(e) != 0;
+#endif
+    return true;
+}
+
 template <int MODE>
 static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool amp_phase)
 {
@@ -2435,13 +2458,19 @@ static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool am
             // a launch told to leave bins alone runs the kCfgKeep build of its kernel; one that writes everything the plain one
             if (A.keep_lo4 > 0 || A.keep_n < kFKeepAll) {
                 constexpr int K = kCfgKeep | kCfgAmpPhase;
+                constexpr int L = K | kCfgLow | kCfgBar;
+                const bool low = f_low_fits(P, A);
                 if (A.sum_partial) {
-                    if (A.cmask && f_band_fits(P, A.band_lo4, A.band_n))
-                        launch_f<FPlan4096, MODE, K | kCfgBar | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
-                    else if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask | kCfgSums>(st, P, A);
+                    if (A.cmask && f_band_fits(P, A.band_lo4, A.band_n)) {
+                        if (low) launch_f<FPlan4096, MODE, L | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
+                        else launch_f<FPlan4096, MODE, K | kCfgBar | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
+                    } else if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask | kCfgSums>(st, P, A);
+                    else if (low) launch_f<FPlan4096, MODE, L | kCfgSums>(st, P, A);
                     else dispatch_f_size<MODE, K | kCfgBar | kCfgSums>(st, P, A);
                 } else if (bar) {
-                    if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask>(st, P, A);
+                    if (low && A.cmask) launch_f<FPlan4096, MODE, L | kCfgCMask>(st, P, A);
+                    else if (low) launch_f<FPlan4096, MODE, L>(st, P, A);
+                    else if (A.cmask) dispatch_f_size<MODE, K | kCfgBar | kCfgCMask>(st, P, A);
                     else dispatch_f_size<MODE, K | kCfgBar>(st, P, A);
                 } else {
                     if (A.cmask) dispatch_f_size<MODE, K | kCfgCMask>(st, P, A);

@@ -138,7 +138,9 @@ void launch_fft_inv(hipStream_t st, const PlanDev &P, size_t npix, const c32 *ff
 // stored amplitudes | unwrapped phases of its traces (the F kernels' kCfgSums, fft_f.hpp; PSums / PHSums of the P and PH kernels; one row per wave from the FBP kernels); a second small launch
 // (launch_sum_axis0 over the rows) makes the pixel sums of them
 // band_lo4 / band_n (multiples of 4; 0, 0 = unknown): the bins outside [band_lo4, band_lo4 + band_n) are zero in `mask` —
-// lets the nt = 4096 chain with a complex multiplier and the sums stage a band-limited table (fft_f.hpp, kCfgBand)
+// lets the nt = 4096 chain with a complex multiplier and the sums stage a band-limited table (fft_f.hpp, kCfgBand).
+// Together with a keep range the pair is a promise: `mask` is exactly zero there and `cmask` finite, and the nt = 4096
+// F chain may leave out the inverse transform's products with those zeros (fft_f.hpp, "band pruning")
 // keep_lo4 / keep_n (multiples of 4): the launch must store the bins [keep_lo4, keep_lo4 + keep_n) of fft_out and
 // amp_out and may leave the others untouched (fft_f.hpp, "keep range"); keep_n < 0 = every bin.  Honoured by the plans
 // pipeline_keeps_range() names; every other plan writes everything.

@@ -487,7 +487,9 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // The multiplier is zero outside [band_lo, band_hi) — checked on the vector itself, a plugin's NaN or Inf times
     // the band pass's zero is not one; a complex multiplier must be finite there — so this launch leaves zeros in
     // d_fft / d_amp outside that range, and where the launch before it did the same only the hull of the two ranges
-    // has to be stored (fft_f.hpp, "keep range").  THZ_F_KEEP_ZEROS=0: developer knob, every launch writes everything.
+    // has to be stored (fft_f.hpp, "keep range"), and a launch with such a range also leaves out of the inverse
+    // transform's input the products with those zeros ("band pruning").
+    // THZ_F_KEEP_ZEROS=0: developer knob, every launch writes and computes everything.
     bool zero_outside = band_known;
     if (const char *e = getenv("THZ_F_KEEP_ZEROS")) zero_outside = zero_outside && atoi(e) != 0;
     for (size_t k = 0; zero_outside && k < nf; ++k) {
