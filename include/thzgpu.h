@@ -422,6 +422,48 @@ int thz_deconvolve(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg, 
                    float dx, float dy, const float *d_in, float *d_out, float *d_img,
                    float *d_gains_out, volatile const int *abort_flag, float *progress);
 
+/* ------------------------------------------------------------------ */
+/* Pulse arrival times and the tilt they imply (K16)    */
+/* ------------------------------------------------------------------ */
+/* Not a reference function: the reference's Tilt Compensation takes two angles typed in by hand
+ * (tilt_compensation.rs:27-32) and nothing says what they should be.  The quantity they describe is when the pulse
+ * arrives at each pixel — also the time-of-flight image of a scan (thickness / depth contrast).
+ *
+ * thz_peak_map: per trace x[0 .. nt) of a (npix, nt) f32 cube, with key = |x| (mode 0), x (mode 1) or -x (mode 2):
+ *   d_index  (npix) int32  position of the largest key.  Of equal keys the lowest index; a NaN never wins; a trace
+ *                          of NaNs gives 0.
+ *   d_value  (npix) f32    x[index], signed, exact
+ *   d_offset (npix) f32    sub-sample vertex of the parabola through x[k-1], x[k], x[k+1]:
+ *                          0.5 (y- - y+) / (y- - 2 y0 + y+) in f32, clamped to [-0.5, 0.5]; exactly 0 for k == 0,
+ *                          k == nt - 1, a zero denominator or a non-finite value among the three
+ * Any output may be NULL.  One streaming read of the cube, the traffic of thz_intensity; d_data needs 4-byte
+ * alignment only.  nt <= 2^30.  Time under THZ_STAGE_PEAK. */
+int thz_peak_map(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data, int mode, int32_t *d_index,
+                 float *d_offset, float *d_value);
+
+/* The ten sums of the least-squares plane tau(u, v) = t0 + a u + b v over an (nx, ny) grid of the three images:
+ * with vmax the largest finite |value|, a pixel takes part iff |value| is finite and >= rel_threshold * vmax (f32);
+ *   u = (i - nx / 2) dx, v = (j - ny / 2) dy   (the centre rule of tilt_compensation.rs:159-164),
+ *   tau = (index + offset) dt_ps               (ps from the axis' first sample)
+ * moments = { S 1, S u, S v, S uu, S uv, S vv, S tau, S u tau, S v tau, S tau tau }, host, added in double in a fixed
+ * order on a fixed launch geometry: the same images give the same ten doubles on every run and every device. */
+int thz_arrival_plane_moments(thz_ctx *ctx, size_t nx, size_t ny, float dx, float dy, double dt_ps,
+                              const int32_t *d_index, const float *d_offset, const float *d_value,
+                              float rel_threshold, double *moments /* 10 */);
+
+/* The plane and the angles that flatten it under the reference's rule delta = (u tilt_x + v tilt_y) / c
+ * (tilt_compensation.rs:171-175, c = 0.299792458 mm / ps): tilt = -slope c radians, reported in degrees. */
+typedef struct thz_tilt_fit {
+    double tilt_x_deg, tilt_y_deg;
+    double slope_x_ps_per_mm, slope_y_ps_per_mm;
+    double t0_ps;   /* the plane at u = v = 0, from the axis' first sample */
+    double rms_ps;  /* root mean square residual of the pixels that took part */
+    uint64_t n_used;
+} thz_tilt_fit;
+/* Solves the plane's normal equations in double from the ten moments; no GPU involved.  THZ_SKIPPED with every field
+ * zero when fewer than 3 pixels took part or the pixels do not span a plane (one row, one column, one line). */
+int thz_host_arrival_plane_fit(const double *moments /* 10 */, thz_tilt_fit *out);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -506,7 +548,10 @@ enum {
     THZ_BUF_AVG_FFT = 6,    /* (nf) complex   — needs want_means */
     THZ_BUF_AVG_AMPLITUDES = 7, /* (nf) */
     THZ_BUF_AVG_PHASES = 8, /* (nf) */
-    THZ_BUF_OPACITY = 9     /* (nx, ny, nt_out) after thz_session_voxels */
+    THZ_BUF_OPACITY = 9,    /* (nx, ny, nt_out) after thz_session_voxels */
+    THZ_BUF_PEAK_INDEX = 10,  /* int32, one per pixel of the grid thz_session_peak_map last mapped */
+    THZ_BUF_PEAK_OFFSET = 11, /* f32, likewise */
+    THZ_BUF_PEAK_VALUE = 12   /* f32, likewise */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -600,6 +645,16 @@ void *thz_session_buffer(thz_session *s, int which);
  * pixel range beyond the grid of the recompute that filled it. */
 int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, void *dst);
 
+/* thz_peak_map on a resident cube: `which` = THZ_BUF_RAW (the raw grid, nt samples) or THZ_BUF_DATA (the last
+ * recompute's grid and final traces, nt_out samples; the deconvolved cube after thz_session_deconvolve).  Fills the
+ * three resident images THZ_BUF_PEAK_INDEX / _OFFSET / _VALUE (thz_session_buffer, thz_session_download; absent until
+ * the first call, and again after an upload).  THZ_ERR_NOT_READY when the cube is absent. */
+int thz_session_peak_map(thz_session *s, int which, int mode);
+/* The map, the moments and the fit in one call: the angles that flatten the arrival plane of `which`.  THZ_BUF_RAW
+ * uses the raw grid's dx / dy and time axis, THZ_BUF_DATA thz_session_grid's and thz_session_time_out's; dt is the
+ * axis' mean step.  Returns thz_host_arrival_plane_fit's code. */
+int thz_session_estimate_tilt(thz_session *s, int which, int mode, float rel_threshold, thz_tilt_fit *out);
+
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */
 /* ------------------------------------------------------------------ */
@@ -683,6 +738,15 @@ int thz_group_session_recompute(thz_group_session *gs, const thz_chain_cfg *cfg,
  * thz_session_deconvolve.  DESIGN.md §5: expected times on 2 / 4 / 8 GPUs from measured phase times. */
 int thz_group_session_deconvolve(thz_group_session *gs, const thz_psf *psf, const thz_deconv_cfg *cfg,
                                  volatile const int *abort_flag, float *progress);
+/* thz_session_estimate_tilt over the whole grid of a group session, bit for bit one session's result on every rank.
+ * Every member maps its own slab (its THZ_BUF_PEAK_* images); the three images go to rank 0 through the gather (the
+ * int32 image as its bits); rank 0 runs the same moments kernels and the same fit on the whole-grid images; the
+ * seven doubles and the count return to every rank as bit patterns through one thz_group_all_reduce_u64 to which the
+ * other ranks add zeros.  Collective and blocking: every rank calls it with the same arguments. */
+int thz_group_session_estimate_tilt(thz_group_session *gs, int which, int mode, float rel_threshold, thz_tilt_fit *out);
+/* the gathered whole-grid maps of the last thz_group_session_estimate_tilt on rank 0's device (NULL elsewhere, or
+ * before the first call): which = THZ_BUF_PEAK_INDEX / _OFFSET / _VALUE */
+void *thz_group_session_peak_result(thz_group_session *gs, int which);
 /* Regions of interest over the whole (nx, ny) grid (thz_session_set_rois): every slab sums its rows of the
  * whole grid's mask — the sampled row index shape0 - y - 1 (math_tools.rs:647) runs along the sharded axis —,
  * the recompute's C2 all-reduces the regions' sums with the pixel sums, and every member divides by the grid's
@@ -836,7 +900,8 @@ enum {
     THZ_STAGE_VOXEL_SELECT = 9,
     THZ_STAGE_VOXEL_EMIT = 10,
     THZ_STAGE_PROBE = 11,
-    THZ_STAGE_COUNT = 12
+    THZ_STAGE_PEAK = 12,
+    THZ_STAGE_COUNT = 13
 };
 /* hipEvent bracketing of every stage call on the context's stream.
  *   0  off (default)

@@ -354,6 +354,18 @@ impl GpuEngine {
         t
     }
 
+    /// The angles that flatten the pulse's arrival plane over the WHOLE grid (`thz_group_session_estimate_tilt`): of the
+    /// raw cube (`which = THZ_BUF_RAW`) or of the chain's final traces (`THZ_BUF_DATA`; whatever the walk has recorded
+    /// is flushed first).  `mode` 0 largest |x|, 1 maximum, 2 minimum.  `None`: no session, no plane, or an error.
+    pub fn estimate_tilt(&mut self, which: c_int, mode: c_int, rel_threshold: f32) -> Option<ThzTiltFit> {
+        if self.session.is_null() { return None; }
+        if which == THZ_BUF_DATA && !self.flush() { return None; }
+        let mut fit: ThzTiltFit = unsafe { std::mem::zeroed() };
+        let rc = unsafe { thz_group_session_estimate_tilt(self.session, which, mode, rel_threshold, &mut fit) };
+        if rc < 0 { log::error!("estimate_tilt: {}", self.last_error()); }
+        if rc == THZ_OK { Some(fit) } else { None }
+    }
+
     /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
     /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
     /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and

@@ -3,9 +3,13 @@
 //! VERBATIM.  Transliteration of `GpuTiltCompensation::filter` (`thz_image_explorer_amd/host/thz_engine.cpp`, tested by
 //! `tests/test_gpu_engine.py`); UNVERIFIED BY A COMPILER.
 //!
+//! ... and ADDS an "Estimate" action to `ui()` (`:237-271`), in front of `final_response`'s return: the two angles
+//! the reference has typed in by hand until the image looks flat, fitted instead to when the pulse arrives at each
+//! pixel of the raw cube (`GpuTiltCompensation::estimate`, same file).
+//!
 //! Add to the file's imports:
 //!     use crate::gpu::engine::ENGINE;
-//!     use crate::gpu::ffi::{thz_host_frequency_axis, thz_host_tilt_plan};
+//!     use crate::gpu::ffi::{thz_host_frequency_axis, thz_host_tilt_plan, THZ_BUF_RAW};
 //!     use crate::math_tools_gpu::shallow_clone;
 
     fn filter(&mut self, input_data: &ScannedImageFilterData, gui_settings: &mut GuiSettingsContainer,
@@ -32,3 +36,17 @@
         }
         output
     }
+
+    // ---- in `ui()`, behind the two sliders (`:261-268`) and in front of `final_response` (`:270`):
+        // the pulse's main peak is its maximum (mode 1); pixels below a quarter of the strongest peak take no part
+        let estimate = ui.button("Estimate").on_hover_text("Fit both angles to the pulse's arrival time over the raw scan");
+        if estimate.clicked() {
+            let fit = ENGINE.lock().unwrap().estimate_tilt(THZ_BUF_RAW, 1, 0.25);
+            if let Some(fit) = fit {
+                self.tilt_x = fit.tilt_x_deg.clamp(-15.0, 15.0); // the sliders' range
+                self.tilt_y = fit.tilt_y_deg.clamp(-15.0, 15.0);
+                // a changed response is how a filter's panel requests ConfigCommand::UpdateFilter(uuid) (filter.rs:650-658)
+                final_response.mark_changed();
+            }
+        }
+        final_response |= estimate;

@@ -10,5 +10,6 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT,
                       BUF_AVG_AMPLITUDES, BUF_AVG_PHASES, BUF_OPACITY, VoxelCfg, VOXEL_INSTANCE, VOXEL_MAX_INSTANCES,
                       voxel_cfg_default, Group, GroupSession, host_slab, group_unique_id, GATHER_SMALL, GATHER_TIME, GATHER_ALL, PipelineIo,
-                      host_optical_properties, host_align_reference, PlotOut, host_gaussian_kernel1d, host_select_step, host_select_value)
+                      host_optical_properties, host_align_reference, PlotOut, host_gaussian_kernel1d, host_select_step, host_select_value,
+                      TiltFit, host_arrival_plane_fit, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, PEAK_ABS, PEAK_MAX, PEAK_MIN)
 from . import binding  # noqa: F401

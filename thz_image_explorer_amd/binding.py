@@ -21,7 +21,8 @@ STATUS = {0: "THZ_OK", -1: "THZ_ERR_INVALID", -2: "THZ_ERR_UNSUPPORTED", -3: "TH
 
 WIN_ADAPTED_BLACKMAN, WIN_BLACKMAN, WIN_HANNING, WIN_HAMMING, WIN_FLAT_TOP = range(5)
 STAGE_FFT, STAGE_FD_MASK, STAGE_IFFT, STAGE_PIPELINE, STAGE_TD_WINDOW, STAGE_INTENSITY, \
-    STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE = range(12)
+    STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE, STAGE_PEAK = range(13)
+PEAK_ABS, PEAK_MAX, PEAK_MIN = range(3)  # thz_peak_map's mode: largest |x|, maximum, minimum
 
 
 class WindowCfg(C.Structure):
@@ -113,7 +114,16 @@ class PlotOut(C.Structure):
 
 
 BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BUF_AVG_AMPLITUDES, \
-    BUF_AVG_PHASES, BUF_OPACITY = range(10)
+    BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE = range(13)
+
+
+class TiltFit(C.Structure):
+    """thz_tilt_fit: the arrival plane and the angles that flatten it"""
+    _fields_ = [("tilt_x_deg", C.c_double), ("tilt_y_deg", C.c_double), ("slope_x_ps_per_mm", C.c_double),
+                ("slope_y_ps_per_mm", C.c_double), ("t0_ps", C.c_double), ("rms_ps", C.c_double), ("n_used", C.c_uint64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
 
 
 class ThzError(RuntimeError):
@@ -224,6 +234,13 @@ SYMBOLS = [
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_float), _P]),
     ("thz_group_session_voxels", C.c_int, [_P, C.POINTER(VoxelCfg), C.c_uint64, C.c_int, _SZ, _SZ, _SZ, _P,
                                            C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float), _P]),
+    ("thz_peak_map", C.c_int, [_P, _SZ, _SZ, _P, C.c_int, _P, _P, _P]),
+    ("thz_arrival_plane_moments", C.c_int, [_P, _SZ, _SZ, C.c_float, C.c_float, C.c_double, _P, _P, _P, C.c_float, _P]),
+    ("thz_host_arrival_plane_fit", C.c_int, [_P, C.POINTER(TiltFit)]),
+    ("thz_session_peak_map", C.c_int, [_P, C.c_int, C.c_int]),
+    ("thz_session_estimate_tilt", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.POINTER(TiltFit)]),
+    ("thz_group_session_estimate_tilt", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.POINTER(TiltFit)]),
+    ("thz_group_session_peak_result", _P, [_P, C.c_int]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -390,6 +407,18 @@ def host_optical_properties(sample_amp, sample_phase, ref_amp, ref_phase, freq, 
     return tuple(out)
 
 
+def host_arrival_plane_fit(moments):
+    """ten moments of thz_arrival_plane_moments -> (status: 0 fitted, 1 skipped; TiltFit)"""
+    m = np.ascontiguousarray(moments, np.float64)
+    if m.size != 10:
+        raise ValueError("ten moments expected")
+    fit = TiltFit()
+    rc = load_library().thz_host_arrival_plane_fit(m.ctypes.data, C.byref(fit))
+    if rc < 0:
+        raise ThzError(rc, "thz_host_arrival_plane_fit")
+    return rc, fit
+
+
 def voxel_cfg_default() -> VoxelCfg:
     cfg = VoxelCfg()
     _rc(load_library().thz_voxel_cfg_default(C.byref(cfg)), "voxel_cfg_default")
@@ -525,6 +554,20 @@ class Session:
                                                         C.byref(n), C.byref(thr), dims.ctypes.data))
         return out[:min(n.value, capacity)], thr.value, tuple(float(x) for x in dims)
 
+    def peak_map(self, which=0, mode=PEAK_ABS):
+        """arrival-time maps of THZ_BUF_RAW / THZ_BUF_DATA -> (index int32, offset f32, value f32), each (gx, gy)"""
+        self.eng._check(self.eng.lib.thz_session_peak_map(self.h, int(which), int(mode)))
+        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        return tuple(self.download(b, npix=gx * gy).reshape(gx, gy) for b in (BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE))
+
+    def estimate_tilt(self, which=0, mode=PEAK_ABS, rel_threshold=0.25):
+        """map + moments + fit -> (status: 0 fitted, 1 skipped; TiltFit)"""
+        fit = TiltFit()
+        rc = self.eng.lib.thz_session_estimate_tilt(self.h, int(which), int(mode), float(rel_threshold), C.byref(fit))
+        if rc < 0:
+            self.eng._check(rc)
+        return rc, fit
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -542,7 +585,9 @@ class Session:
         nf = nto // 2 + 1
         per = {BUF_RAW: (self.nt,), BUF_FFT: (nf, 2), BUF_AMPLITUDES: (nf,), BUF_PHASES: (nf,), BUF_DATA: (nto,),
                BUF_IMG: (), BUF_OPACITY: (nto,)}
-        if which in per:
+        if which in (BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE):  # npix: the mapped grid's, from the caller
+            out = np.empty(npix, np.int32 if which == BUF_PEAK_INDEX else np.float32)
+        elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
             out = np.empty((npix,) + per[which], np.float32)
@@ -696,6 +741,27 @@ class GroupSession:
             out = np.empty((nf, 2) if which == BUF_AVG_FFT else (nf,), np.float32)
             self.g._check(self.g.lib.thz_group_session_download(self.h, which, 0, 1, out.ctypes.data))
         return out
+
+    def estimate_tilt(self, which=0, mode=PEAK_ABS, rel_threshold=0.25):
+        """thz_session_estimate_tilt over the whole grid (collective) -> (status, TiltFit), the same on every rank"""
+        fit = TiltFit()
+        rc = self.g.lib.thz_group_session_estimate_tilt(self.h, int(which), int(mode), float(rel_threshold), C.byref(fit))
+        if rc < 0:
+            self.g._check(rc)
+        return rc, fit
+
+    def peak_maps(self, npix):
+        """the gathered whole-grid maps of the last estimate_tilt on rank 0 -> (index, offset, value), npix each"""
+        out = []
+        for which, dt in ((BUF_PEAK_INDEX, np.int32), (BUF_PEAK_OFFSET, np.float32), (BUF_PEAK_VALUE, np.float32)):
+            p = self.g.lib.thz_group_session_peak_result(self.h, which)
+            if not p:
+                raise ThzError(-4, "the arrival-time maps are not on this process")
+            a = np.empty(npix, dt)
+            eng = self.g.engine(self.g.ranks.index(0))
+            eng._check(eng.lib.thz_memcpy_d2h(eng.ctx, a.ctypes.data, _P(p), a.nbytes))
+            out.append(a)
+        return tuple(out)
 
     def voxels(self, cfg: "VoxelCfg", max_instances=VOXEL_MAX_INSTANCES, scaling=1, orig_dims=None, capacity=None):
         """the 3-D tab's instances over the WHOLE grid (collective: every rank calls it) ->
@@ -872,6 +938,16 @@ class Engine:
 
     def apply_td_window(self, npix, d_in, win, d_out):
         self._check(self.lib.thz_apply_td_window(self.ctx, npix, _dp(d_in), _dp(win), _dp(d_out)))
+
+    def peak_map(self, npix, nt, data, mode, index=None, offset=None, value=None):
+        """per-trace arrival: index (int32), sub-sample offset and signed value of the extreme sample"""
+        self._check(self.lib.thz_peak_map(self.ctx, npix, nt, _dp(data), int(mode), _dp(index), _dp(offset), _dp(value)))
+
+    def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
+        m = np.zeros(10, np.float64)
+        self._check(self.lib.thz_arrival_plane_moments(self.ctx, nx, ny, dx, dy, dt_ps, _dp(index), _dp(offset), _dp(value),
+                                                       rel_threshold, m.ctypes.data))
+        return m
 
     def intensity(self, npix, data, img):
         self._check(self.lib.thz_intensity(self.ctx, npix, _dp(data), _dp(img)))

@@ -35,6 +35,10 @@ struct thz_group_session {
     // gathered copies on rank 0's device, allocated when first asked for
     float *d_img = nullptr, *d_data = nullptr, *d_fft = nullptr, *d_amp = nullptr, *d_ph = nullptr;
     size_t cap_img = 0, cap_data = 0, cap_fft = 0, cap_amp = 0, cap_ph = 0;  // floats allocated
+    // gathered arrival-time maps of the last thz_group_session_estimate_tilt (group_tilt.cpp), on rank 0's device:
+    // [index bits | offsets | values], cap_peak entries each of which the first peak_pix are the grid's
+    float *d_peak = nullptr;
+    size_t cap_peak = 0, peak_pix = 0;
     std::vector<size_t> cur_rows;      // rows of the outputs' grid per rank (the block grid behind a scaling stage)
     size_t cur_ny = 0;
     size_t cur_pix() const

@@ -139,7 +139,7 @@ void thz_group_session_destroy(thz_group_session *gs)
     for (thz_session *s : gs->sess) thz_session_destroy(s);
     if (gs->root_local >= 0) {
         (void)hipSetDevice(gs->g->m[(size_t)gs->root_local].ctx->device);
-        for (float *p : {gs->d_img, gs->d_data, gs->d_fft, gs->d_amp, gs->d_ph})
+        for (float *p : {gs->d_img, gs->d_data, gs->d_fft, gs->d_amp, gs->d_ph, gs->d_peak})
             if (p) (void)hipFree(p);
     }
     delete gs;

@@ -55,6 +55,11 @@ struct thz_session {
     float *d_opacity = nullptr;                // voxel opacities of the final cube (thz_session_voxels)
     size_t opacity_floats = 0;
     int32_t *d_ins = nullptr;
+    // arrival-time maps of the last thz_session_peak_map (peak_api.cpp): one entry per pixel of the grid it mapped
+    int32_t *d_peak_index = nullptr;
+    float *d_peak_offset = nullptr, *d_peak_value = nullptr;
+    size_t peak_cap = 0;                       // pixels allocated
+    size_t peak_nx = 0, peak_ny = 0;           // the mapped grid; 0 x 0: the maps are absent
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;
@@ -145,5 +150,14 @@ int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only);
 int session_roi_finish(thz_session *s, const thz_chain_cfg *cfg, bool data_only);
 size_t session_roi_floats(const thz_session *s);
 void session_roi_free(thz_session *s);
+// peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA) with its grid, trace length and the mean step of
+// its time axis; THZ_ERR_NOT_READY when it is absent
+struct SessionCube {
+    const float *d = nullptr;
+    size_t nx = 0, ny = 0, nt = 0;
+    float dx = 1.0f, dy = 1.0f;
+    double dt_ps = 0.0;
+};
+int session_cube(thz_session *s, int which, SessionCube *out);
 // the ifft stage's avg_data (avg_in_fourier_space; needs the means): host-side, after session_means
 int session_avg_data(thz_session *s, const thz_chain_cfg *cfg);

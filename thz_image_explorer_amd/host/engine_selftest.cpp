@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <fstream>
 #include <string>
+#include <cstring>
 #include <vector>
 
 using namespace thzhost;
@@ -222,6 +223,17 @@ int main(int argc, char **argv)
         q.open(c.raw.data(), (size_t)c.nx, (size_t)c.ny, c.time, c.dx, c.dy);
         q.filter_data[0].pixel_selected = {3, 2};
         q.filter_data[0].rois = p.filter_data[0].rois;
+        // the arrival plane of the raw cube: two slabs give one session's fit bit for bit, and the plugin's
+        // "Estimate" action writes exactly those angles into its fields
+        thz_tilt_fit fit1{}, fit2{};
+        const int rc1 = eng.estimate_tilt(THZ_BUF_RAW, 1, 0.25f, fit1), rc2 = eng2.estimate_tilt(THZ_BUF_RAW, 1, 0.25f, fit2);
+        std::printf("estimate_tilt: %d / %d, %.6f / %.6f degrees over %llu pixels, rms %.4f ps\n", rc1, rc2, fit1.tilt_x_deg, fit1.tilt_y_deg,
+                    (unsigned long long)fit1.n_used, fit1.rms_ps);
+        CHECK(rc1 == THZ_OK && rc2 == THZ_OK && fit1.n_used > 0, "estimate_tilt on one slab and on two");
+        CHECK(std::memcmp(&fit1, &fit2, sizeof fit1) == 0, "estimate_tilt over two slabs == over one");
+        GpuTiltCompensation tilt_plugin;
+        CHECK(tilt_plugin.estimate(eng2) && tilt_plugin.tilt_x == fit1.tilt_x_deg && tilt_plugin.tilt_y == fit1.tilt_y_deg,
+              "the Tilt plugin's Estimate action writes the fitted angles");
         *dynamic_cast<FrequencyDomainBandPass *>(q.filter_by("Frequency Band Pass")) = *fd;
         dynamic_cast<TimeDomainBandPassBeforeFFT *>(q.filter_by("Band-Pass Filter in Time Domain after the FFT."))->high = tda->high;
         q.config = p.config;

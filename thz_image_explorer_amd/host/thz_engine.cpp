@@ -350,6 +350,13 @@ bool GpuEngine::voxels(const thz_voxel_cfg &cfg, uint64_t max_instances, size_t 
     out.resize((size_t)(n < cap ? n : cap));
     return true;
 }
+int GpuEngine::estimate_tilt(int which, int mode, float rel_threshold, thz_tilt_fit &out)
+{
+    out = thz_tilt_fit{};
+    if (!session_) return THZ_ERR_NOT_READY;
+    if (which == THZ_BUF_DATA && !flush()) return THZ_ERR_NOT_READY;
+    return thz_group_session_estimate_tilt(session_, which, mode, rel_threshold, &out);
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;
@@ -489,6 +496,15 @@ ScannedImageFilterData GpuTiltCompensation::filter(const ScannedImageFilterData 
         thz_host_frequency_axis(new_time.data(), new_time.size(), output.frequency.data());
     }
     return output;
+}
+
+bool GpuTiltCompensation::estimate(GpuEngine &eng)
+{
+    thz_tilt_fit fit{};
+    if (eng.estimate_tilt(THZ_BUF_RAW, estimate_mode, estimate_threshold, fit) != THZ_OK) return false;
+    tilt_x = fit.tilt_x_deg;
+    tilt_y = fit.tilt_y_deg;
+    return true;
 }
 
 // selected pixel's trace of the current results, for the Time Band Pass plots (after the flush: deferred show_data)

@@ -68,6 +68,10 @@ public:
     // the whole cube, every slab's instances in x, y, z order — what one GPU gives for the same cube
     bool voxels(const thz_voxel_cfg &cfg, uint64_t max_instances, size_t scaling, size_t orig_w, size_t orig_h,
                 size_t orig_d, std::vector<thz_voxel_instance> &out, float &threshold, float cube_dims[3]);
+    // The angles that flatten the pulse's arrival plane over the WHOLE grid (thz_group_session_estimate_tilt): of the raw
+    // cube (which = THZ_BUF_RAW) or of the chain's final traces (THZ_BUF_DATA; whatever the walk has recorded is
+    // flushed first).  mode 0 largest |x|, 1 maximum, 2 minimum.  THZ_OK, THZ_SKIPPED (no plane: `out` is zeros) or < 0
+    int estimate_tilt(int which, int mode, float rel_threshold, thz_tilt_fit &out);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
@@ -101,6 +105,11 @@ bool finish_stage_walk(GpuEngine &eng, ScannedImageFilterData &last, const Confi
 
 // ---- the plugins on the engine (rust/filters/*.rs): same structs, `filter()` records ------------------------
 struct GpuTiltCompensation : TiltCompensation {
+    // the "Estimate" action of the plugin's panel: the raw cube's arrival plane -> tilt_x / tilt_y; the caller then
+    // requests UpdateFilter(<this filter>) as for a moved slider.  false (fields untouched) when there is no plane
+    int estimate_mode = 1;                 // the pulse's main peak is its maximum
+    float estimate_threshold = 0.25f;      // pixels below a quarter of the strongest peak take no part
+    bool estimate(GpuEngine &eng);
     ScannedImageFilterData filter(const ScannedImageFilterData &, GuiSettingsContainer &, ProgressLock &,
                                   const std::atomic<bool> &) override;
     std::unique_ptr<Filter> clone_box() const override { return std::make_unique<GpuTiltCompensation>(*this); }
