@@ -464,6 +464,40 @@ typedef struct thz_tilt_fit {
  * zero when fewer than 3 pixels took part or the pixels do not span a plane (one row, one column, one line). */
 int thz_host_arrival_plane_fit(const double *moments /* 10 */, thz_tilt_fit *out);
 
+/* ------------------------------------------------------------------ */
+/* Optical-property maps (K17)                          */
+/* ------------------------------------------------------------------ */
+/* calculate_optical_properties (math_tools.rs:663-701; thz_host_optical_properties) for every pixel of a scan, as means
+ * over bands of bins.  The reference computes one vector (the selected pixel or a region's mean, data_thread.rs:1489-1559)
+ * from absolute unwrapped phases.  Per pixel that is not enough: numpy_unwrap starts at bin 0, in the noise, so each
+ * pixel's phase reaches the band with its own multiple of 2 pi.  The anchor removes it: over the bins [anchor_k0,
+ * anchor_k1) the least-squares line delta_k = b + s k through delta_k = phase[p, k] - ref_phase[k] is fitted in double;
+ * m = rint(b / 2 pi) (b: the line at bin 0; m = 0 when b is not finite) and the pixel's phases enter the formula as
+ * fl32(phase - w), w = (float)(m 2 pi).  anchor_k0 == anchor_k1: no anchor, m = 0, w = +0 — the reference's own
+ * absolute phases.  Per bin k of a band the values are the reference's f32 formula in its operation order (IEEE division
+ * and fmaxf; no special case for a thickness <= 0, zero amplitudes or NaN):
+ *   d_n, d_alpha, d_kappa  (n_bands, npix) f32, band-major: the mean over the band's bins [band_k0, band_k1), added in
+ *                          f32 in an order that depends on the arguments alone (same inputs, same bits)
+ *   d_wraps                (npix) int32: m
+ *   d_slope                (npix) f32: (float)s, rad per bin — the group delay of the pixel against the reference: the
+ *                          pixel's pulse arrives -s nt / (2 pi) samples after the reference's
+ * Any output may be NULL.  d_amp, d_phase: (npix, nf) f32 on the device, 4-byte alignment; ref_amp, ref_phase, freq
+ * (THz): nf host floats; d_thickness: one thickness per pixel (device, npix) or NULL for cfg->thickness everywhere.
+ * One launch; only the anchor's and the bands' bins of each row are read.  THZ_ERR_INVALID before any launch unless
+ * n_bands <= THZ_OPTICAL_MAX_BANDS, every band has 1 <= k0 < k1 <= nf (bin 0 has omega = 0) and the anchor has at least
+ * two bins or none, and ends at nf or before.  npix == 0 is a no-op.  Time under THZ_STAGE_OPTICAL. */
+#define THZ_OPTICAL_MAX_BANDS 8
+typedef struct thz_optical_cfg {
+    float thickness;               /* sample_thickness as the reference passes it; unused where a thickness image is given */
+    uint32_t anchor_k0, anchor_k1; /* [a0, a1); equal = off */
+    uint32_t n_bands;
+    uint32_t band_k0[8], band_k1[8];
+} thz_optical_cfg;
+int thz_optical_maps(thz_ctx *ctx, size_t npix, size_t nf, const float *d_amp, const float *d_phase,
+                     const float *ref_amp, const float *ref_phase, const float *freq, const thz_optical_cfg *cfg,
+                     const float *d_thickness, float *d_n, float *d_alpha, float *d_kappa, int32_t *d_wraps,
+                     float *d_slope);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -551,7 +585,12 @@ enum {
     THZ_BUF_OPACITY = 9,    /* (nx, ny, nt_out) after thz_session_voxels */
     THZ_BUF_PEAK_INDEX = 10,  /* int32, one per pixel of the grid thz_session_peak_map last mapped */
     THZ_BUF_PEAK_OFFSET = 11, /* f32, likewise */
-    THZ_BUF_PEAK_VALUE = 12   /* f32, likewise */
+    THZ_BUF_PEAK_VALUE = 12,  /* f32, likewise */
+    THZ_BUF_OPT_N = 13,       /* (n_bands, npix) f32 of the last thz_session_optical_maps, band-major */
+    THZ_BUF_OPT_ALPHA = 14,   /* likewise */
+    THZ_BUF_OPT_KAPPA = 15,   /* likewise */
+    THZ_BUF_OPT_WRAPS = 16,   /* (npix) int32 */
+    THZ_BUF_OPT_SLOPE = 17    /* (npix) f32 */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -654,6 +693,18 @@ int thz_session_peak_map(thz_session *s, int which, int mode);
  * uses the raw grid's dx / dy and time axis, THZ_BUF_DATA thz_session_grid's and thz_session_time_out's; dt is the
  * axis' mean step.  Returns thz_host_arrival_plane_fit's code. */
 int thz_session_estimate_tilt(thz_session *s, int which, int mode, float rel_threshold, thz_tilt_fit *out);
+
+/* thz_optical_maps on the resident amplitudes and phases of the last recompute, on its grid (thz_session_grid) and with
+ * the frequency axis of its time axis (thz_host_frequency_axis of thz_session_time_out).  ref_amp / ref_phase: nf host
+ * floats, e.g. thz_reference_spectrum's; nf must be nt_out / 2 + 1 (THZ_ERR_INVALID).  THZ_ERR_NOT_READY when no
+ * recompute has run since the last upload.  Reads the two arrays in place: the next recompute still knows their zeros.
+ * Fills the five resident images THZ_BUF_OPT_N / _ALPHA / _KAPPA / _WRAPS / _SLOPE (thz_session_buffer,
+ * thz_session_download; absent until the first call, and again after an upload).  For the three band-major ones the
+ * pix0 / npix of thz_session_download count over the flattened (band, pixel) array of the last call.
+ * A group has no form of its own: call this on thz_group_session_member(gs, i) with that slab's rows of the thickness
+ * image; every pixel is independent, so the slabs' maps are the whole grid's rows. */
+int thz_session_optical_maps(thz_session *s, const float *ref_amp, const float *ref_phase, size_t nf,
+                             const thz_optical_cfg *cfg, const float *d_thickness);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */
@@ -901,7 +952,8 @@ enum {
     THZ_STAGE_VOXEL_EMIT = 10,
     THZ_STAGE_PROBE = 11,
     THZ_STAGE_PEAK = 12,
-    THZ_STAGE_COUNT = 13
+    THZ_STAGE_OPTICAL = 13,
+    THZ_STAGE_COUNT = 14
 };
 /* hipEvent bracketing of every stage call on the context's stream.
  *   0  off (default)

@@ -366,6 +366,49 @@ impl GpuEngine {
         if rc == THZ_OK { Some(fit) } else { None }
     }
 
+    /// Refractive index, absorption and extinction over every pixel this process holds, as means over `cfg`'s bands
+    /// (`thz_session_optical_maps` on each local member's resident spectra, the slabs' rows one after the other; whatever
+    /// the walk has recorded is flushed first).  `ref_amp` / `ref_phase`: a reference's `roi_signal_fft` /
+    /// `roi_phase_fft` (`nt_out / 2 + 1` values, `OpenRef`); `cfg`: `sample_thickness`, the anchor and the bands as bin
+    /// ranges.  -> (n, alpha, kappa: (n_bands, gx, gy); wraps, slope: (gx, gy); gx; gy)
+    pub fn optical_maps(&mut self, ref_amp: &[f32], ref_phase: &[f32], cfg: &ThzOpticalCfg)
+                        -> Option<(Vec<f32>, Vec<f32>, Vec<f32>, Vec<i32>, Vec<f32>, usize, usize)> {
+        if self.session.is_null() || ref_amp.len() != ref_phase.len() || !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy) = (0usize, 0usize);
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                if thz_session_optical_maps(s, ref_amp.as_ptr(), ref_phase.as_ptr(), ref_amp.len(), cfg, ptr::null()) != THZ_OK { return None; }
+                thz_session_grid(s, &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                gx += rows[i as usize];
+            }
+            let (nb, npix) = (cfg.n_bands as usize, gx * gy);
+            let (mut n, mut alpha, mut kappa) = (vec![0f32; nb * npix], vec![0f32; nb * npix], vec![0f32; nb * npix]);
+            let (mut wraps, mut slope) = (vec![0i32; npix], vec![0f32; npix]);
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                for b in 0..nb { // a member's maps are band-major over ITS pixels
+                    if thz_session_download(s, THZ_BUF_OPT_N, b * mine, mine, n.as_mut_ptr().add(b * npix + at) as *mut c_void) != THZ_OK
+                        || thz_session_download(s, THZ_BUF_OPT_ALPHA, b * mine, mine, alpha.as_mut_ptr().add(b * npix + at) as *mut c_void) != THZ_OK
+                        || thz_session_download(s, THZ_BUF_OPT_KAPPA, b * mine, mine, kappa.as_mut_ptr().add(b * npix + at) as *mut c_void) != THZ_OK {
+                        return None;
+                    }
+                }
+                if thz_session_download(s, THZ_BUF_OPT_WRAPS, 0, mine, wraps.as_mut_ptr().add(at) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_OPT_SLOPE, 0, mine, slope.as_mut_ptr().add(at) as *mut c_void) != THZ_OK {
+                    return None;
+                }
+                at += mine;
+            }
+            Some((n, alpha, kappa, wraps, slope, gx, gy))
+        }
+    }
+
     /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
     /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
     /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and

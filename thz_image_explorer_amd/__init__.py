@@ -11,5 +11,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       BUF_AVG_AMPLITUDES, BUF_AVG_PHASES, BUF_OPACITY, VoxelCfg, VOXEL_INSTANCE, VOXEL_MAX_INSTANCES,
                       voxel_cfg_default, Group, GroupSession, host_slab, group_unique_id, GATHER_SMALL, GATHER_TIME, GATHER_ALL, PipelineIo,
                       host_optical_properties, host_align_reference, PlotOut, host_gaussian_kernel1d, host_select_step, host_select_value,
-                      TiltFit, host_arrival_plane_fit, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, PEAK_ABS, PEAK_MAX, PEAK_MIN)
+                      TiltFit, host_arrival_plane_fit, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, PEAK_ABS, PEAK_MAX, PEAK_MIN,
+                      OpticalCfg, optical_cfg, OPTICAL_MAX_BANDS, STAGE_OPTICAL, BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA,
+                      BUF_OPT_WRAPS, BUF_OPT_SLOPE)
 from . import binding  # noqa: F401

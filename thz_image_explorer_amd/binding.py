@@ -21,7 +21,8 @@ STATUS = {0: "THZ_OK", -1: "THZ_ERR_INVALID", -2: "THZ_ERR_UNSUPPORTED", -3: "TH
 
 WIN_ADAPTED_BLACKMAN, WIN_BLACKMAN, WIN_HANNING, WIN_HAMMING, WIN_FLAT_TOP = range(5)
 STAGE_FFT, STAGE_FD_MASK, STAGE_IFFT, STAGE_PIPELINE, STAGE_TD_WINDOW, STAGE_INTENSITY, \
-    STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE, STAGE_PEAK = range(13)
+    STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE, STAGE_PEAK, \
+    STAGE_OPTICAL = range(14)
 PEAK_ABS, PEAK_MAX, PEAK_MIN = range(3)  # thz_peak_map's mode: largest |x|, maximum, minimum
 
 
@@ -114,7 +115,9 @@ class PlotOut(C.Structure):
 
 
 BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BUF_AVG_AMPLITUDES, \
-    BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE = range(13)
+    BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, \
+    BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE = range(18)
+OPTICAL_MAX_BANDS = 8
 
 
 class TiltFit(C.Structure):
@@ -124,6 +127,24 @@ class TiltFit(C.Structure):
 
     def as_tuple(self):
         return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+class OpticalCfg(C.Structure):
+    """thz_optical_cfg: thickness, anchor range and bands of thz_optical_maps"""
+    _fields_ = [("thickness", C.c_float), ("anchor_k0", C.c_uint32), ("anchor_k1", C.c_uint32), ("n_bands", C.c_uint32),
+                ("band_k0", C.c_uint32 * 8), ("band_k1", C.c_uint32 * 8)]
+
+
+def optical_cfg(thickness, anchor, bands) -> OpticalCfg:
+    """anchor: (a0, a1) bins or None for none; bands: list of (k0, k1) bin ranges.  More than OPTICAL_MAX_BANDS bands
+    keep their count (the library refuses it) but only the first eight ranges"""
+    cfg = OpticalCfg()
+    cfg.thickness = float(thickness)
+    cfg.anchor_k0, cfg.anchor_k1 = (0, 0) if anchor is None else (int(anchor[0]), int(anchor[1]))
+    cfg.n_bands = len(bands)
+    for i, (k0, k1) in enumerate(list(bands)[:OPTICAL_MAX_BANDS]):
+        cfg.band_k0[i], cfg.band_k1[i] = int(k0), int(k1)
+    return cfg
 
 
 class ThzError(RuntimeError):
@@ -241,6 +262,8 @@ SYMBOLS = [
     ("thz_session_estimate_tilt", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.POINTER(TiltFit)]),
     ("thz_group_session_estimate_tilt", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.POINTER(TiltFit)]),
     ("thz_group_session_peak_result", _P, [_P, C.c_int]),
+    ("thz_optical_maps", C.c_int, [_P, _SZ, _SZ, _P, _P, _P, _P, _P, C.POINTER(OpticalCfg), _P, _P, _P, _P, _P, _P]),
+    ("thz_session_optical_maps", C.c_int, [_P, _P, _P, _SZ, C.POINTER(OpticalCfg), _P]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -568,6 +591,22 @@ class Session:
             self.eng._check(rc)
         return rc, fit
 
+    def optical_maps(self, ref_amp, ref_phase, cfg: "OpticalCfg", thickness=None):
+        """thz_session_optical_maps on the last recompute's amplitudes and phases -> (n, alpha, kappa: (n_bands, gx, gy)
+        f32; wraps (gx, gy) int32; slope (gx, gy) f32).  thickness: device pointer / DevBuf of one f32 per pixel, or None
+        for cfg.thickness everywhere"""
+        ra, rp = (np.ascontiguousarray(x, np.float32) for x in (ref_amp, ref_phase))
+        if ra.size != rp.size:
+            raise ValueError("reference amplitudes and phases differ in length")
+        self.eng._check(self.eng.lib.thz_session_optical_maps(self.h, ra.ctypes.data, rp.ctypes.data, ra.size, C.byref(cfg),
+                                                              _dp(thickness)))
+        gx, gy = self.grid()[:2]
+        nb = int(cfg.n_bands)
+        bands = [self.download(b, npix=nb * gx * gy).reshape(nb, gx, gy) if nb else np.empty((0, gx, gy), np.float32)
+                 for b in (BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA)]
+        return (*bands, self.download(BUF_OPT_WRAPS, npix=gx * gy).reshape(gx, gy),
+                self.download(BUF_OPT_SLOPE, npix=gx * gy).reshape(gx, gy))
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -587,6 +626,8 @@ class Session:
                BUF_IMG: (), BUF_OPACITY: (nto,)}
         if which in (BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE):  # npix: the mapped grid's, from the caller
             out = np.empty(npix, np.int32 if which == BUF_PEAK_INDEX else np.float32)
+        elif BUF_OPT_N <= which <= BUF_OPT_SLOPE:  # npix: entries of the last call's (band, pixel) array, from the caller
+            out = np.empty(npix, np.int32 if which == BUF_OPT_WRAPS else np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -942,6 +983,16 @@ class Engine:
     def peak_map(self, npix, nt, data, mode, index=None, offset=None, value=None):
         """per-trace arrival: index (int32), sub-sample offset and signed value of the extreme sample"""
         self._check(self.lib.thz_peak_map(self.ctx, npix, nt, _dp(data), int(mode), _dp(index), _dp(offset), _dp(value)))
+
+    def optical_maps(self, npix, nf, amp, phase, ref_amp, ref_phase, freq, cfg: "OpticalCfg", thickness=None, n=None,
+                     alpha=None, kappa=None, wraps=None, slope=None):
+        """thz_optical_maps: amp, phase (npix, nf), thickness (npix) and the outputs are device pointers / DevBufs;
+        ref_amp, ref_phase, freq host vectors of nf floats"""
+        host = [np.ascontiguousarray(x, np.float32) for x in (ref_amp, ref_phase, freq)]
+        if any(h.size != nf for h in host):
+            raise ValueError("ref_amp, ref_phase and freq hold nf values each")
+        self._check(self.lib.thz_optical_maps(self.ctx, npix, nf, _dp(amp), _dp(phase), *[h.ctypes.data for h in host],
+                                              C.byref(cfg), _dp(thickness), _dp(n), _dp(alpha), _dp(kappa), _dp(wraps), _dp(slope)))
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

@@ -60,6 +60,12 @@ struct thz_session {
     float *d_peak_offset = nullptr, *d_peak_value = nullptr;
     size_t peak_cap = 0;                       // pixels allocated
     size_t peak_nx = 0, peak_ny = 0;           // the mapped grid; 0 x 0: the maps are absent
+    // optical-property maps of the last thz_session_optical_maps (optical_api.cpp):
+    // d_opt = [n | alpha | kappa: (opt_bands, opt_pix) each | slope: opt_pix]
+    float *d_opt = nullptr;
+    int32_t *d_opt_wraps = nullptr;
+    size_t opt_floats = 0, opt_wraps_cap = 0;  // allocated
+    size_t opt_pix = 0, opt_bands = 0;         // pixels and bands of the last call; 0 pixels: the maps are absent
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;

@@ -101,7 +101,8 @@ void thz_session_destroy(thz_session *s)
                     (void *)s->d_img, (void *)s->d_avg, (void *)s->d_vec, (void *)s->d_tilt, (void *)s->d_ins,
                     (void *)s->d_opacity, (void *)s->d_deconv, (void *)s->d_deconv_img, (void *)s->d_scaled,
                     (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out,
-                    (void *)s->d_peak_index, (void *)s->d_peak_offset, (void *)s->d_peak_value})
+                    (void *)s->d_peak_index, (void *)s->d_peak_offset, (void *)s->d_peak_value, (void *)s->d_opt,
+                    (void *)s->d_opt_wraps})
         if (p) (void)hipFree(p);
     if (s->h_vec) (void)hipHostFree(s->h_vec);
     session_roi_free(s);
@@ -120,6 +121,7 @@ int thz_session_upload(thz_session *s, const float *cube, int subtract_bias)
     s->scale = 1; s->nx_cur = s->nx; s->ny_cur = s->ny; s->dx_cur = s->dx; s->dy_cur = s->dy;
     ++s->src_gen;  // new source traces: the regions' kept sums of them are void
     s->peak_nx = s->peak_ny = 0;  // ... and so are the arrival-time maps
+    s->opt_pix = s->opt_bands = 0;  // ... and the optical-property maps
     if (cube) HIP_TRY(ctx, hipMemcpyAsync(s->d_raw, cube, npix * s->nt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     launch_intensity(ctx->stream, npix, (int)s->nt, s->d_raw, s->d_img, subtract_bias ? 1 : 0);
     if (int rc = check_launch(ctx)) return rc;
@@ -712,6 +714,18 @@ const void *session_buffer_ro(thz_session *s, int which)
         return which == THZ_BUF_PEAK_INDEX ? (const void *)s->d_peak_index
                : which == THZ_BUF_PEAK_OFFSET ? (const void *)s->d_peak_offset : (const void *)s->d_peak_value;
     }
+    // the optical-property maps belong to the spectra of the recompute they were taken of
+    if (which >= THZ_BUF_OPT_N && which <= THZ_BUF_OPT_SLOPE) {
+        if (!s->opt_pix) return nullptr;
+        const size_t plane = s->opt_bands * s->opt_pix;
+        switch (which) {
+        case THZ_BUF_OPT_N: return s->opt_bands ? s->d_opt : nullptr;
+        case THZ_BUF_OPT_ALPHA: return s->opt_bands ? s->d_opt + plane : nullptr;
+        case THZ_BUF_OPT_KAPPA: return s->opt_bands ? s->d_opt + 2 * plane : nullptr;
+        case THZ_BUF_OPT_WRAPS: return s->d_opt_wraps;
+        default: return s->d_opt + 3 * plane;
+        }
+    }
     // Before the first recompute (and between an upload and the next recompute) the output buffers hold
     // nothing a caller may read — and after a scaled recompute they are sized for the smaller grid while
     // the session's grid is the raw one again: absent (NULL / THZ_ERR_NOT_READY) until a recompute has run.
@@ -744,8 +758,11 @@ int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, vo
     // per-pixel outputs were allocated for out_pix pixels by the recompute that filled them; the image has
     // nx * ny entries (allocated once) of which the current grid's are valid
     const bool peak = which == THZ_BUF_PEAK_INDEX || which == THZ_BUF_PEAK_OFFSET || which == THZ_BUF_PEAK_VALUE;
+    const bool opt_band = which == THZ_BUF_OPT_N || which == THZ_BUF_OPT_ALPHA || which == THZ_BUF_OPT_KAPPA;
     const size_t total_pix = which == THZ_BUF_RAW ? s->nx * s->ny
                              : peak ? s->peak_nx * s->peak_ny
+                             : opt_band ? s->opt_bands * s->opt_pix  // the flattened (band, pixel) array
+                             : (which == THZ_BUF_OPT_WRAPS || which == THZ_BUF_OPT_SLOPE) ? s->opt_pix
                              : which == THZ_BUF_IMG ? s->nx_cur * s->ny_cur
                                                     : (s->out_pix < s->nx_cur * s->ny_cur ? s->out_pix : s->nx_cur * s->ny_cur);
     switch (which) {
@@ -754,6 +771,7 @@ int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, vo
     case THZ_BUF_AMPLITUDES: case THZ_BUF_PHASES: per = s->nf_out; break;
     case THZ_BUF_DATA: case THZ_BUF_OPACITY: per = s->nt_out; break;
     case THZ_BUF_IMG: case THZ_BUF_PEAK_INDEX: case THZ_BUF_PEAK_OFFSET: case THZ_BUF_PEAK_VALUE: per = 1; break;  // 4 bytes each
+    case THZ_BUF_OPT_N: case THZ_BUF_OPT_ALPHA: case THZ_BUF_OPT_KAPPA: case THZ_BUF_OPT_WRAPS: case THZ_BUF_OPT_SLOPE: per = 1; break;
     case THZ_BUF_AVG_FFT: return thz_memcpy_d2h(ctx, dst, base, 2 * s->nf_out * sizeof(float));
     case THZ_BUF_AVG_AMPLITUDES: case THZ_BUF_AVG_PHASES: return thz_memcpy_d2h(ctx, dst, base, s->nf_out * sizeof(float));
     default: return THZ_ERR_INVALID;

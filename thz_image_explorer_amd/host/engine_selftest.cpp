@@ -243,6 +243,30 @@ int main(int argc, char **argv)
         q.update_filter(q.index_of("Band-Pass Filter in Time Domain after the FFT."));
         std::vector<float> before;
         CHECK(eng2.download_final(before), "download_final");
+        {
+            // optical-property maps against the scan's own mean spectrum, on one slab and on two: the slabs' maps are the
+            // whole grid's rows (a slab's kernels may pair other traces than one session's, so the last bits may differ)
+            std::vector<std::complex<float>> avg_fft;
+            std::vector<float> ref_amp, ref_phase, n1, a1, k1, s1, n2, a2, k2, s2;
+            std::vector<int32_t> w1, w2;
+            CHECK(eng2.averages(avg_fft, ref_amp, ref_phase), "averages");
+            const size_t nf = ref_amp.size();
+            thz_optical_cfg oc{};
+            oc.thickness = 1e-3f;
+            oc.anchor_k0 = (uint32_t)(nf / 10 + 1); oc.anchor_k1 = (uint32_t)(nf / 2);
+            oc.n_bands = 2;
+            oc.band_k0[0] = oc.anchor_k0; oc.band_k1[0] = oc.anchor_k1;
+            oc.band_k0[1] = 1; oc.band_k1[1] = (uint32_t)nf;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0;
+            CHECK(eng.optical_maps(ref_amp, ref_phase, oc, n1, a1, k1, w1, s1, gx1, gy1), "optical_maps on one slab");
+            CHECK(eng2.optical_maps(ref_amp, ref_phase, oc, n2, a2, k2, w2, s2, gx2, gy2), "optical_maps on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1, "optical_maps: the whole grid");
+            CHECK(n2.size() == 2 * gx1 * gy1 && k2.size() == n2.size() && w2.size() == gx1 * gy1 && s2.size() == w2.size(), "optical_maps: sizes");
+            double worst = 0.0;
+            for (size_t i = 0; i < s1.size(); ++i) worst = std::fmax(worst, std::fabs((double)s1[i] - s2[i]));
+            std::printf("optical_maps: slope over two slabs against one, largest difference %.3g rad / bin\n", worst);
+            CHECK(worst < 1e-4, "optical_maps over two slabs == over one (slope)");
+        }
         small_bank(q.filter_by("Deconvolution"));
         q.filters_active[q.filter_chain[q.index_of("Deconvolution")]] = true;
         q.update_filter(q.index_of("Deconvolution"));

@@ -357,6 +357,44 @@ int GpuEngine::estimate_tilt(int which, int mode, float rel_threshold, thz_tilt_
     if (which == THZ_BUF_DATA && !flush()) return THZ_ERR_NOT_READY;
     return thz_group_session_estimate_tilt(session_, which, mode, rel_threshold, &out);
 }
+bool GpuEngine::optical_maps(const std::vector<float> &ref_amp, const std::vector<float> &ref_phase, const thz_optical_cfg &cfg,
+                             std::vector<float> &n, std::vector<float> &alpha, std::vector<float> &kappa, std::vector<int32_t> &wraps,
+                             std::vector<float> &slope, size_t &gx, size_t &gy)
+{
+    gx = gy = 0;
+    if (!session_ || ref_amp.size() != ref_phase.size() || !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        if (thz_session_optical_maps(s, ref_amp.data(), ref_phase.data(), ref_amp.size(), &cfg, nullptr) != THZ_OK) return false;
+        thz_session_grid(s, &rows[(size_t)i], &gy, nullptr, nullptr);
+        gx += rows[(size_t)i];
+    }
+    const size_t nb = cfg.n_bands, npix = gx * gy;
+    n.assign(nb * npix, 0.0f);
+    alpha.assign(nb * npix, 0.0f);
+    kappa.assign(nb * npix, 0.0f);
+    wraps.assign(npix, 0);
+    slope.assign(npix, 0.0f);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = rows[(size_t)i] * gy;
+        if (!mine) continue;
+        for (size_t b = 0; b < nb; ++b) {  // a member's maps are band-major over ITS pixels
+            if (thz_session_download(s, THZ_BUF_OPT_N, b * mine, mine, n.data() + b * npix + at) != THZ_OK
+                || thz_session_download(s, THZ_BUF_OPT_ALPHA, b * mine, mine, alpha.data() + b * npix + at) != THZ_OK
+                || thz_session_download(s, THZ_BUF_OPT_KAPPA, b * mine, mine, kappa.data() + b * npix + at) != THZ_OK)
+                return false;
+        }
+        if (thz_session_download(s, THZ_BUF_OPT_WRAPS, 0, mine, wraps.data() + at) != THZ_OK
+            || thz_session_download(s, THZ_BUF_OPT_SLOPE, 0, mine, slope.data() + at) != THZ_OK)
+            return false;
+        at += mine;
+    }
+    return true;
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;

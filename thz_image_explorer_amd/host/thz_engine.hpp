@@ -72,6 +72,14 @@ public:
     // cube (which = THZ_BUF_RAW) or of the chain's final traces (THZ_BUF_DATA; whatever the walk has recorded is
     // flushed first).  mode 0 largest |x|, 1 maximum, 2 minimum.  THZ_OK, THZ_SKIPPED (no plane: `out` is zeros) or < 0
     int estimate_tilt(int which, int mode, float rel_threshold, thz_tilt_fit &out);
+    // Refractive index, absorption and extinction over every pixel this process holds, as means over cfg's bands
+    // (thz_session_optical_maps on each local member's resident spectra, the slabs' rows one after the other; whatever
+    // the walk has recorded is flushed first).  ref_amp / ref_phase: a reference's roi_signal_fft / roi_phase_fft
+    // (nt_out / 2 + 1 values, OpenRef); cfg: sample_thickness, the anchor and the bands as bin ranges.
+    // n, alpha, kappa: (n_bands, gx, gy); wraps, slope: (gx, gy)
+    bool optical_maps(const std::vector<float> &ref_amp, const std::vector<float> &ref_phase, const thz_optical_cfg &cfg,
+                      std::vector<float> &n, std::vector<float> &alpha, std::vector<float> &kappa, std::vector<int32_t> &wraps,
+                      std::vector<float> &slope, size_t &gx, size_t &gy);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
