@@ -31,23 +31,29 @@ static_assert(sizeof(cx) == 8, "cx must alias c32");
 struct alignas(16) cx2 {
     cx a, b;
 };
-__device__ __forceinline__ cx cx_mul_pk(cx a, cx b);
 __device__ __forceinline__ cx cx_mul(cx a, cx b)
 {
-#ifdef THZ_CX_MUL_ASM  // A/B builds (scripts/gpu_ab_builds.py): every complex product through cx_mul_pk
-    return cx_mul_pk(a, b);
-#else
     const cx bs = {-b.y, b.x};
     return a.xx * b + a.yy * bs;
-#endif
 }
 // The same product in two instructions: hipcc builds {-b.y, b.x} with a v_xor and a v_mov in front of every cx_mul
 // whose b is not loop-invariant (it folds the broadcasts a.xx / a.yy into op_sel, but not a one-sided negation or a
 // swap), i.e. four VALU instructions and a wait state per product.  Here the negation and the swap ride on the
 // first instruction's modifiers:  t = {-a.y b.y, a.y b.x};  r = {a.x b.x + t.x, a.x b.y + t.y}.
-// A packed-fp32 result needs one wait state before a dependent VALU reads it (the compiler's own listings put an
-// s_nop 0 there); inline asm is opaque to its hazard recognizer, so the wait states are written out.
-// Same roundings as cx_mul as hipcc compiles it: a.y's products rounded, a.x's fused onto them.
+// Inline asm is opaque to hipcc's hazard recognizer, so the wait states are written out: one in front (an operand's
+// writer may be a packed-fp32 instruction), one between the multiply and the fused multiply-add that reads it, one
+// behind.  By the rule hipcc's listings follow (see cx_mul_batch below: a wait state only behind a packed writer whose
+// op_sel_hi[0] is set) the one behind the fma is not needed; it stays because this form's users (the staged complex
+// multiplier, k_dc_energy_edges) keep their machine code as measured.  Whether that rule is the hardware's or only the
+// compiler's caution the listings cannot say; a spare s_nop 0 is harmless either way.
+// Same roundings as cx_mul as hipcc compiles it: a.y's products rounded, a.x's fused onto them.  The sign flip rides on
+// a.y here (neg_lo:[1,0]) and on b.y in cx_mul and cx_mul_batch (neg_lo:[0,1]): the same value for every operand that
+// is a number, but where a.y or b.y is a NaN this form can hand on that NaN with the other sign, so it is not a
+// bit-for-bit stand-in for cx_mul on NaN inputs and the batches are.
+// For a product that stands alone (a multiplier fresh from LDS, registers to spare for nothing else).  Three wait states
+// and a scheduling fence per product: sent through this one by one, every product of the nt = 4096 chain trades 275 VALU
+// instructions for 1 191 s_nop and spills (profiles/cx_products_instruction_counts.txt) — where several independent
+// products meet, cx_mul_batch below.
 __device__ __forceinline__ cx cx_mul_pk(cx a, cx b)
 {
 #ifdef THZ_EMU
@@ -64,6 +70,83 @@ __device__ __forceinline__ cx cx_mul_pk(cx a, cx b)
         : "v"(a), "v"(b));
     return r;
 #endif
+}
+// K independent products in 2 K issue slots:  out[i] = ax[i].xx * b[i] + ay[i].yy * {-b[i].y, b[i].x}  (ax = ay = a:
+// a[i] * b[i]; the R2C / C2R splits take the two splats from different values).  One statement of K multiplies followed
+// by K fused multiply-adds accumulating in place, so each product's second instruction sits K slots behind its first.
+// Wait states, from hipcc's own listings of these kernels: it puts one independent instruction or an s_nop 0 between a
+// packed-fp32 instruction and a VALU read of its result exactly where the writer's op_sel_hi[0] is set (the default of
+// v_pk_add/mul, and the multiply below), and nothing behind a writer with op_sel_hi[0] clear (its own cx_mul's
+// v_pk_fma ... op_sel_hi:[0,1,1], the fused multiply-add below, whose result it reads in the very next instruction).
+// (That is the rule of the compiler's hazard recognizer as its output shows it; the hardware may ask for less.)
+// So: K >= 2 covers the multiplies; the statement opens with one s_nop 0 because the instruction in front of it may be
+// such a writer of an operand, which hipcc cannot pad for what is inside the string; nothing is needed behind it.
+// The sign flip rides on b.y, where hipcc's v_xor puts it, and the roundings are cx_mul's as hipcc compiles it (a.y's
+// products rounded, a.x's fused onto them): the same bits, NaNs included.
+// SA: ax / ay are wave-uniform (compile-time constants) and go in SGPR pairs instead of costing two v_mov each.
+#ifndef THZ_EMU
+#define THZ_PKM(o, ay, b) "v_pk_mul_f32 %" #o ", %" #ay ", %" #b " op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
+#define THZ_PKF(o, ax, b) "v_pk_fma_f32 %" #o ", %" #ax ", %" #b ", %" #o " op_sel_hi:[0,1,1]\n\t"
+#define THZ_PK_BATCH2(CA) \
+    asm("s_nop 0\n\t" THZ_PKM(0, 4, 6) THZ_PKM(1, 5, 7) THZ_PKF(0, 2, 6) THZ_PKF(1, 3, 7) \
+        : "=&v"(out[0]), "=&v"(out[1]) \
+        : CA(ax[0]), CA(ax[1]), CA(ay[0]), CA(ay[1]), "v"(b[0]), "v"(b[1]))
+#define THZ_PK_BATCH3(CA) \
+    asm("s_nop 0\n\t" THZ_PKM(0, 6, 9) THZ_PKM(1, 7, 10) THZ_PKM(2, 8, 11) THZ_PKF(0, 3, 9) THZ_PKF(1, 4, 10) THZ_PKF(2, 5, 11) \
+        : "=&v"(out[0]), "=&v"(out[1]), "=&v"(out[2]) \
+        : CA(ax[0]), CA(ax[1]), CA(ax[2]), CA(ay[0]), CA(ay[1]), CA(ay[2]), "v"(b[0]), "v"(b[1]), "v"(b[2]))
+#define THZ_PK_BATCH4(CA) \
+    asm("s_nop 0\n\t" THZ_PKM(0, 8, 12) THZ_PKM(1, 9, 13) THZ_PKM(2, 10, 14) THZ_PKM(3, 11, 15) \
+        THZ_PKF(0, 4, 12) THZ_PKF(1, 5, 13) THZ_PKF(2, 6, 14) THZ_PKF(3, 7, 15) \
+        : "=&v"(out[0]), "=&v"(out[1]), "=&v"(out[2]), "=&v"(out[3]) \
+        : CA(ax[0]), CA(ax[1]), CA(ax[2]), CA(ax[3]), CA(ay[0]), CA(ay[1]), CA(ay[2]), CA(ay[3]), \
+          "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]))
+#define THZ_PK_BATCH5(CA) \
+    asm("s_nop 0\n\t" THZ_PKM(0, 10, 15) THZ_PKM(1, 11, 16) THZ_PKM(2, 12, 17) THZ_PKM(3, 13, 18) THZ_PKM(4, 14, 19) \
+        THZ_PKF(0, 5, 15) THZ_PKF(1, 6, 16) THZ_PKF(2, 7, 17) THZ_PKF(3, 8, 18) THZ_PKF(4, 9, 19) \
+        : "=&v"(out[0]), "=&v"(out[1]), "=&v"(out[2]), "=&v"(out[3]), "=&v"(out[4]) \
+        : CA(ax[0]), CA(ax[1]), CA(ax[2]), CA(ax[3]), CA(ax[4]), CA(ay[0]), CA(ay[1]), CA(ay[2]), CA(ay[3]), CA(ay[4]), \
+          "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]))
+#endif
+template <int K, bool SA = false>
+__device__ __forceinline__ void cx_mul2_batch(cx *out, const cx *ax, const cx *ay, const cx *b)
+{
+    static_assert(K >= 2, "a lone product has nothing to put between its two instructions: cx_mul_pk");
+#ifdef THZ_EMU
+    for (int i = 0; i < K; ++i) {
+        const cx bs = {-b[i].y, b[i].x};
+        out[i] = ax[i].xx * b[i] + ay[i].yy * bs;
+    }
+#else
+    if constexpr (K > 5) {  // an asm statement takes 30 operands at most: statements of four, the last of two to five
+        cx_mul2_batch<4, SA>(out, ax, ay, b);
+        cx_mul2_batch<K - 4, SA>(out + 4, ax + 4, ay + 4, b + 4);
+    } else if constexpr (SA) {
+        if constexpr (K == 2) THZ_PK_BATCH2("s");
+        else if constexpr (K == 3) THZ_PK_BATCH3("s");
+        else if constexpr (K == 4) THZ_PK_BATCH4("s");
+        else THZ_PK_BATCH5("s");
+    } else {
+        if constexpr (K == 2) THZ_PK_BATCH2("v");
+        else if constexpr (K == 3) THZ_PK_BATCH3("v");
+        else if constexpr (K == 4) THZ_PK_BATCH4("v");
+        else THZ_PK_BATCH5("v");
+    }
+#endif
+}
+#ifndef THZ_EMU
+#undef THZ_PK_BATCH5
+#undef THZ_PK_BATCH4
+#undef THZ_PK_BATCH3
+#undef THZ_PK_BATCH2
+#undef THZ_PKF
+#undef THZ_PKM
+#endif
+// out[i] = a[i] * b[i], bit for bit cx_mul's.  out may not alias a or b: every multiply writes before any operand dies.
+template <int K, bool SA = false>
+__device__ __forceinline__ void cx_mul_batch(cx (&out)[K], const cx (&a)[K], const cx (&b)[K])
+{
+    cx_mul2_batch<K, SA>(out, a, a, b);
 }
 __device__ __forceinline__ cx cx_conj(cx a) { return cx{a.x, -a.y}; }
 __device__ __forceinline__ cx cx_mnegi(cx a) { return cx{a.y, -a.x}; }  // a * (-i)
@@ -325,17 +408,77 @@ constexpr double kFTwoPi = 6.28318530717958647692528676655900577;
 constexpr float f_unit_re(int e, int d) { return (float)f_small_cos(kFTwoPi * e / d); }
 constexpr float f_unit_im(int e, int d) { return (float)-f_small_sin(kFTwoPi * e / d); }
 
+// One group of four k1 of the compact pass 1 with its products batched (cx_mul_batch): the twiddle rows this group
+// still lacks (tw[1], [2], [4], [8] come from the table; group 0 also builds row 5 and group 1 leaves it out, so that
+// no product stands alone), odd x row with the constants W_N^k1 in SGPRs, then the data products two k1 at a time.
+// The products, their operands and the order of the LDS stores are those of the loop in f_core_pass1.
+template <class P, int G>
+__device__ __forceinline__ void f_pass1_compact_group(cx (&r)[P::C1][P::R1], cx (&tw)[P::R1], cx (&otw)[P::R1], cx *buf,
+                                                      const FAddr<P> &ad)
+{
+    constexpr int M1 = P::M1;
+    if constexpr (G <= 1) {
+        cx o[2];
+        const cx a[2] = {tw[G + 1], tw[2 * G + 1]}, b[2] = {tw[2 + 2 * G], tw[4]};  // 3 = 1 2, 5 = 1 4 | 6 = 2 4, 7 = 3 4
+        cx_mul_batch<2>(o, a, b);
+        tw[G == 0 ? 3 : 6] = o[0];
+        tw[G == 0 ? 5 : 7] = o[1];
+    } else {
+        constexpr int first = (G == 2) ? 9 : 12, n = (G == 2) ? 3 : 4;  // k1 = (k1 - 8) 8
+        cx o[n], a[n], b[n];
+#pragma unroll
+        for (int i = 0; i < n; ++i) {
+            a[i] = tw[first + i - 8];
+            b[i] = tw[8];
+        }
+        cx_mul_batch<n>(o, a, b);
+#pragma unroll
+        for (int i = 0; i < n; ++i) tw[first + i] = o[i];
+    }
+    {
+        constexpr int first = (G == 0) ? 1 : 4 * G, n = 4 * G + 4 - first;
+        cx o[n], a[n], b[n];
+#pragma unroll
+        for (int i = 0; i < n; ++i) {
+            a[i] = cx{f_unit_re(first + i, P::N), f_unit_im(first + i, P::N)};  // W_N^k1
+            b[i] = tw[first + i];
+        }
+        cx_mul_batch<n, true>(o, a, b);
+#pragma unroll
+        for (int i = 0; i < n; ++i) otw[first + i] = o[i];
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int k1 = 4 * G + 2 * h;  // a constant once unrolled
+        if (k1 == 0) {                  // G = 0, h = 0 only: k1 = 0 has no twiddle, so a batch of two
+            cx o[2];
+            const cx a[2] = {r[0][1], r[1][1]}, b[2] = {tw[1], otw[1]};
+            cx_mul_batch<2>(o, a, b);
+            st2(buf + ad.w1[1] + M1, o[0], o[1]);  // = e1(1, 2*lane + {0,1})
+        } else {
+            cx o[4];
+            const cx a[4] = {r[0][k1], r[1][k1], r[0][k1 + 1], r[1][k1 + 1]};
+            const cx b[4] = {tw[k1], otw[k1], tw[k1 + 1], otw[k1 + 1]};
+            cx_mul_batch<4>(o, a, b);
+            st2(buf + ad.w1[k1 & 3] + k1 * M1, o[0], o[1]);  // = e1(k1, 2*lane + {0,1})
+            st2(buf + ad.w1[(k1 + 1) & 3] + (k1 + 1) * M1, o[2], o[3]);
+        }
+    }
+    THZ_SCHED_FENCE();
+}
+
 // COMPACT (k_f at nt = 4096, FPlan::T1_COMPACT): t1 points to T1c[r][lane] = W_N^(2 lane 2^r), r = 0..3, and the
 // twiddle of (m, k1) = (2 lane + b, k1) is built as
 //     W_N^(2 lane k1) = product of the rows of k1's bits  (at most three multiplies deep: 7 = (1 2) 4, 15 = 7 8)
 //     W_N^((2 lane + 1) k1) = that  x  W_N^k1              (a compile-time constant)
 // — 26 complex multiplies per pass where the full table costs 15 16-byte LDS reads, and 14 KiB of LDS less.
-// PK: twiddle products through cx_mul_pk (two VALU instructions each instead of four)
+// PK (with COMPACT): the products in batches, two VALU instructions each instead of four (f_pass1_compact_group)
 template <class P, bool COMPACT = false, bool PK = false>
 __device__ __forceinline__ void f_core_pass1(cx (&r)[P::C1][P::R1], cx *buf, const cx *t1,
                                              const FAddr<P> &ad, int lane)
 {
     constexpr int R1 = P::R1, C1 = P::C1, M1 = P::M1;
+    static_assert(!PK || COMPACT, "batched products: the compact form only");
     // ---- pass 1
 #pragma unroll
     for (int c = 0; c < C1; ++c) {
@@ -351,6 +494,15 @@ __device__ __forceinline__ void f_core_pass1(cx (&r)[P::C1][P::R1], cx *buf, con
         tw[4] = tc[2 * kWave];
         tw[8] = tc[3 * kWave];
         st2(buf + ad.w1[0], r[0][0], r[1][0]);
+        if constexpr (PK) {
+            cx otw[R1];
+            f_pass1_compact_group<P, 0>(r, tw, otw, buf, ad);
+            f_pass1_compact_group<P, 1>(r, tw, otw, buf, ad);
+            f_pass1_compact_group<P, 2>(r, tw, otw, buf, ad);
+            f_pass1_compact_group<P, 3>(r, tw, otw, buf, ad);
+            wave_sync();
+            return;
+        }
 #pragma unroll
         for (int k1 = 1; k1 < R1; ++k1) {
             if (k1 == 3) tw[3] = cx_mul(tw[1], tw[2]);
@@ -374,13 +526,13 @@ __device__ __forceinline__ void f_core_pass1(cx (&r)[P::C1][P::R1], cx *buf, con
             cx v0 = r[0][k1], v1 = r[1][k1];
             if (k1 > 0) {
                 const cx2 w = ld2(t1l + k1 * M1);
-                v0 = PK ? cx_mul_pk(v0, w.a) : cx_mul(v0, w.a);
-                v1 = PK ? cx_mul_pk(v1, w.b) : cx_mul(v1, w.b);
+                v0 = cx_mul(v0, w.a);
+                v1 = cx_mul(v1, w.b);
             }
             st2(buf + ad.w1[k1 & 3] + k1 * M1, v0, v1);  // = e1(k1, 2*lane + {0,1})
         } else {
             cx v = r[0][k1];
-            if (k1 > 0) v = PK ? cx_mul_pk(v, t1l[k1 * M1]) : cx_mul(v, t1l[k1 * M1]);
+            if (k1 > 0) v = cx_mul(v, t1l[k1 * M1]);
             buf[ad.w1[k1 & 3] + k1 * M1] = v;  // = e1(k1, lane)
         }
         if ((k1 & 3) == 3) THZ_SCHED_FENCE();
@@ -408,7 +560,9 @@ __device__ __forceinline__ void f_core_pass1_regs(cx (&r)[1][P::R1], cx *buf, co
 
 // KEEP (C3 = 1): the transform's outputs Z[lane + 64 k3] stay in `keep` instead of going to LDS in natural order — for
 // a consumer that only reduces over them
-template <class P, bool PK = false, bool KEEP = false>
+// PK: the pass-2 twiddle products 0 as hipcc compiles cx_mul, 1 one by one through cx_mul_pk (k_dc_energy_edges: at
+// 128 VGPRs it has no room for a batch's early-clobber outputs and spills with them), 2 in batches (cx_mul_batch)
+template <class P, int PK = 0, bool KEEP = false>
 __device__ __forceinline__ void f_core_pass23(cx *buf, const cx *t2, const FAddr<P> &ad, int lane, cx (*keep)[P::R3] = nullptr)
 {
     constexpr int R1 = P::R1, R2 = P::R2, R3 = P::R3, C2 = P::C2, C3 = P::C3;
@@ -428,6 +582,30 @@ __device__ __forceinline__ void f_core_pass23(cx *buf, const cx *t2, const FAddr
     for (int c2 = 0; c2 < C2; ++c2) {
         dftR<R2>(b[c2]);
         THZ_SCHED_FENCE();
+        if constexpr (PK == 2) {
+            // the four products between two fences as one batch (three in front of the first); same stores, same order
+#pragma unroll
+            for (int g = 0; g < R2 / 4; ++g) {
+                cx v[4], w[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] = t2l[(4 * g + i) * 8];
+                if (g == 0) {
+                    v[0] = b[c2][0];
+                    cx_mul2_batch<3>(v + 1, b[c2] + 1, b[c2] + 1, w + 1);
+                } else {
+                    cx_mul2_batch<4>(v, b[c2] + 4 * g, b[c2] + 4 * g, w);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k2 = 4 * g + i;
+                    constexpr int kq = R1 / 4;
+                    const int variant = (((k2 * kq) & 3) >> 1) ^ c2;
+                    buf[ad.w2[variant & 1] + (k2 * R1 * 8 + 8 * c2 * 8)] = v[i];  // = e2(row, j3), as below
+                }
+                THZ_SCHED_FENCE();
+            }
+            continue;
+        }
 #pragma unroll
         for (int k2 = 0; k2 < R2; ++k2) {
             cx v = b[c2][k2];
@@ -506,24 +684,31 @@ __device__ __forceinline__ cx f_w2n_from_row0(cx t)
 // Written on p = a + b, m = a - b (s = {p.x, m.y}, d = {m.x, p.y}): the conjugate never exists as a
 // value, the multiply takes its splats straight from p and m, and X[N-k] comes out unconjugated —
 // a conj() of a packed value is a negate plus a move here, as is building {b.x, -b.y}.
+// (t = d * w2 comes from r2c_pair's own product, or from a batch of four: cx_mul2_batch(t, m, p, w2))
+__device__ __forceinline__ void r2c_tail(cx p, cx m, cx t, cx &xk, cx &xn)
+{
+    xk = cx{fmaf(p.x, 0.5f, t.x), fmaf(m.y, 0.5f, t.y)};
+    xn = cx{fmaf(p.x, 0.5f, -t.x), fmaf(-m.y, 0.5f, t.y)};  // conj(s/2 - t)
+}
 __device__ __forceinline__ void r2c_pair(cx a, cx b, cx w2, cx &xk, cx &xn)
 {
     const cx p = a + b, m = a - b;
     const cx bs = {-w2.y, w2.x};
     const cx t = m.xx * w2 + p.yy * bs;  // d * w2
-    xk = cx{fmaf(p.x, 0.5f, t.x), fmaf(m.y, 0.5f, t.y)};
-    xn = cx{fmaf(p.x, 0.5f, -t.x), fmaf(-m.y, 0.5f, t.y)};  // conj(s/2 - t)
+    r2c_tail(p, m, t, xk, xn);
 }
 
 // swap(Z'[k]) — the inverse core takes its input with re/im exchanged — from X[k], X[N-k] (as stored,
 // unconjugated) and wc = conj(w2):  Z' = E + i (D conj(w)) = E + 2 D wc  with E = {p.x, m.y},
 // D = {m.x, p.y}, p = X[k] + X[N-k], m = X[k] - X[N-k].  Same idea as r2c_pair: no conjugate is ever
 // built, and the two FMAs write the exchanged pair directly.
+// (t = D * wc: c2r_swapped_pm's own product, or one of a batch, cx_mul2_batch(t, m, p, wc))
+__device__ __forceinline__ cx c2r_swapped_tail(cx p, cx m, cx t) { return cx{fmaf(2.0f, t.y, m.y), fmaf(2.0f, t.x, p.x)}; }
 __device__ __forceinline__ cx c2r_swapped_pm(cx p, cx m, cx wc)
 {
     const cx bs = {-wc.y, wc.x};
     const cx t = m.xx * wc + p.yy * bs;  // D * wc
-    return cx{fmaf(2.0f, t.y, m.y), fmaf(2.0f, t.x, p.x)};
+    return c2r_swapped_tail(p, m, t);
 }
 __device__ __forceinline__ cx c2r_swapped(cx xk, cx xn, cx wc) { return c2r_swapped_pm(xk + xn, xk - xn, wc); }
 // One-term forms: the other term is a product with a zero of the multiplier (kCfgLow).  x + (+-0) and x - (+-0) are x
@@ -908,8 +1093,9 @@ struct FSums {
 // per group spread over the whole epilogue; only the Nyquist bin is still stored here.
 // KEEP (fused chain): amplitudes and bin N are stored inside the keep range only; keep_lo / keep_n come back as the
 // range this trace's stores obey — FArgs' own, or every bin for a non-finite trace — for f_inverse_input.
+// PK: the split's products in batches (cx_mul_batch)
 template <class P, bool AMP_PHASE, bool CMASK = false, bool SUMS = false, bool WC = false, bool STORE_FFT = true, bool BAND = false,
-          bool KEEP = false>
+          bool KEEP = false, bool PK = false>
 __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, const cx *wg_s,
                                                     const float *mask, size_t p, const FArgs &A,
                                                     int lane, FSums<P> *sums = nullptr, int *keep_lo = nullptr,
@@ -956,6 +1142,28 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
         if (g < NG / 2) {
             cx *zm = buf - 256 * g;
             const cx wg = wg_s[(256 / P::M1) * g];  // w2n[256 g], wave-uniform
+            if constexpr (PK) {
+                // the loop below with the group's four wl[c] wg and its four d w2 as one batch each; the bins of the
+                // four pairs are distinct, so reading all of them before writing any changes nothing
+                cx w2[4], pp[4], mm[4], t[4];
+                const cx wg4[4] = {wg, wg, wg, wg};
+                cx_mul_batch<4>(w2, wl, wg4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const cx a = zf[fb[c]], b = zm[mb[c]];
+                    pp[c] = a + b;
+                    mm[c] = a - b;
+                }
+                cx_mul2_batch<4>(t, mm, pp, w2);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    cx xk, xn;
+                    r2c_tail(pp[c], mm[c], t[c], xk, xn);
+                    X[c] = xk;
+                    zf[fb[c]] = xk;  // X[k]
+                    zm[mb[c]] = xn;  // X[N-k]
+                }
+            } else
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const cx a = zf[fb[c]], b = zm[mb[c]];
@@ -1127,8 +1335,9 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
 // LOW (kCfgLow, with KEEP): the multiplier is zero at every bin >= N/2 + M1 and the keep range ends there at the
 // latest.  X[n] H[n] is then a zero for j1 >= R1/2 + 1 and X[N-n] H[N-n] for j1 <= R1/2 - 2: those half-terms — two
 // LDS reads, the multiply, the split's adds, the spectrum store of the former — are left out at compile time.
+// PK (C1 = 2): the products in batches (cx_mul_batch)
 template <class P, bool MASKED, bool CMASK = false, bool WC = false, bool STORE = false, bool BAND = false, bool KEEP = false,
-          bool LOW = false>
+          bool LOW = false, bool PK = false>
 __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, const cx *wg_s,
                                                 const float *__restrict__ mask, int lane,
                                                 cx (&r)[P::C1][P::R1], cx *fft_row = nullptr, int band_off = 0, int band_cap = 0,
@@ -1139,6 +1348,7 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
 #pragma clang fp contract(off)
     static_assert(!STORE || MASKED, "the stored spectrum is the masked one");
     static_assert(!LOW || (KEEP && STORE), "the pruned form is the fused chain's with a keep range");
+    static_assert(!PK || P::C1 == 2, "batches of four: two j1 times two columns");
     constexpr int N = P::N, R1 = P::R1, C1 = P::C1, M1 = P::M1;
     cx wlc[C1];  // conj of the lane's staged twiddles: the product below is conj(w2) directly
     if constexpr (WC) {
@@ -1174,15 +1384,33 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
     const FRow frow = f_row(reinterpret_cast<float *>(fft_row + (STORE && KEEP ? keep_lo : 0)), STORE && KEEP && keep_bins > 0 ? 8u * (unsigned)keep_bins : 0u);
     float *frow_all = reinterpret_cast<float *>(fft_row) + 2 * mk_f;  // !KEEP: every bin, plain stores
     const int rel = KEEP ? launder_v(8 * (mk_f - keep_lo)) : 0;
+    // The loop below holds both forms side by side, told apart at compile time.  Without PK: wc = wl[c] wg per bin and
+    // the split right behind it; wcq, pq and mq are never touched.  With PK: the wc of the loop body is a plain copy that
+    // nothing reads; the products are made per pair of j1 (wcq at even j1, D wc at odd j1).  Giving the two forms bodies
+    // of their own (tried: wc inside `if constexpr (!PK)`) changes the register allocation of the measured builds.
+    cx wcq[2 * C1], pq[2 * C1], mq[2 * C1];  // PK: wc, p and m of a pair of j1
 #pragma unroll
     for (int j1 = 0; j1 < R1; ++j1) {
         const cx wgc = cx_conj(wg_s[j1]);  // conj(w2n[M1 j1]), wave-uniform
+        if constexpr (PK) {
+            // the split twiddles of this j1 and the next, and further down their products D wc, as one batch per pair of j1
+            if (j1 == 0) {
+                const cx g1[C1] = {cx_conj(wg_s[1]), cx_conj(wg_s[1])};
+                cx_mul_batch<C1>(*reinterpret_cast<cx(*)[C1]>(wcq + C1), wlc, g1);
+#pragma unroll
+                for (int c = 0; c < C1; ++c) wcq[c] = wlc[c];
+            } else if ((j1 & 1) == 0) {
+                const cx gn = cx_conj(wg_s[j1 + 1]);
+                const cx a4[2 * C1] = {wlc[0], wlc[1], wlc[0], wlc[1]}, g4[2 * C1] = {wgc, wgc, gn, gn};
+                cx_mul_batch<2 * C1>(wcq, a4, g4);
+            }
+        }
         const bool has_f = !LOW || j1 <= R1 / 2, has_m = !LOW || j1 >= R1 / 2 - 1;  // (compile-time: j1 is unrolled)
         cx kept[C1];
 #pragma unroll
         for (int c = 0; c < C1; ++c) {
             const int off = M1 * j1 + c;
-            const cx wc = j1 == 0 ? wlc[c] : cx_mul(wlc[c], wgc);
+            const cx wc = PK ? wlc[c] : j1 == 0 ? wlc[c] : cx_mul(wlc[c], wgc);  // (PK: wcq, in the pair's batch)
             cx xk = cx{0.0f, 0.0f}, xn = cx{0.0f, 0.0f};
             if (has_f) xk = buf[fbase[j1 & 1][c] + M1 * j1];
             if (has_m) xn = buf[mbase[j1 & 1][c] - M1 * j1];
@@ -1213,7 +1441,21 @@ __device__ __forceinline__ void f_inverse_input(const cx *buf, const cx *w2n_s, 
                 if (has_m) xn = cx{xn.x * mn, xn.y * mn};
             }
             kept[c] = xk;
-            r[c][j1] = !has_m ? c2r_swapped_fwd(xk, wc) : !has_f ? c2r_swapped_mir(xn, wc) : c2r_swapped(xk, xn, wc);
+            if constexpr (PK) {
+                // c2r_swapped_fwd / _mir / c2r_swapped's p and m; the products wait for the pair of j1 to be complete
+                pq[C1 * (j1 & 1) + c] = !has_m ? xk : !has_f ? xn : xk + xn;
+                mq[C1 * (j1 & 1) + c] = !has_m ? xk : !has_f ? -xn : xk - xn;
+            } else {
+                r[c][j1] = !has_m ? c2r_swapped_fwd(xk, wc) : !has_f ? c2r_swapped_mir(xn, wc) : c2r_swapped(xk, xn, wc);
+            }
+        }
+        if constexpr (PK) {
+            if ((j1 & 1) == 1) {
+                cx t[2 * C1];
+                cx_mul2_batch<2 * C1>(t, mq, pq, wcq);  // D * wc
+#pragma unroll
+                for (int i = 0; i < 2 * C1; ++i) r[i % C1][j1 - 1 + i / C1] = c2r_swapped_tail(pq[i], mq[i], t[i]);
+            }
         }
         if constexpr (STORE) {
             // bins M1 j1 + C1 lane (+ 1), 8 bytes each; the offset is formed here, not sixteen of them up front
@@ -1354,6 +1596,12 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     const int wib = THZ_UNIFORM((int)(threadIdx.x >> 6));
     const int wpb = (int)(blockDim.x >> 6);
     constexpr bool TC = P::T1_COMPACT;  // compact pass-1 twiddles (FPlan): t1 = T1c[r][lane], no staged w2n head
+    // Complex products in batches of two-instruction pairs (cx_mul_batch): the fused nt = 4096 chain, which is bound by
+    // the vector pipe's issue slots.  The other builds keep hipcc's four-instruction form and their register counts.
+    constexpr bool PKB = TC && MODE == kPipe;
+    // f_inverse_input's batches hold a pair of j1 at a time, 16 VGPRs more: the builds without the block barrier sit at
+    // 251-255 VGPRs and would spill 8-10 of them, so their inverse input stays as it was
+    constexpr bool PKI = PKB && (CFG & kCfgBar) != 0;
     cx *t1 = reinterpret_cast<cx *>(lds);
     cx *t2 = t1 + P::KF_T1_ENTRIES;
     float *mask_s = reinterpret_cast<float *>(t2 + P::T2_ENTRIES);
@@ -1517,9 +1765,9 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
             // The next trace of this wave is prefetched into registers right
             // after pass 1 (of the inverse transform in the fused chain): `r` is dead
             // by then, so the 16 KiB of prefetch registers never coexist with it.
-            f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+            f_core_pass1<P, TC, PKB>(r, buf, t1, ad, lane);
             if (MODE == kFwd && p + stride < A.npix) f_load_raw<P>(A.in + (p + stride) * NT, lane, raw);
-            f_core_pass23<P>(buf, t2, ad, lane);
+            f_core_pass23<P, PKB ? 2 : 0>(buf, t2, ad, lane);
             if (MODE == kFwd) f_land_prefetch<P>(raw);
         } else {
             // prefetched spectrum -> LDS in the nat() layout, X[N] at buf[N]
@@ -1543,19 +1791,19 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
             f_inverse_input<P, false, false, TC>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
                                                  nullptr, lane, r);
             wave_sync();
-            f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+            f_core_pass1<P, TC, PKB>(r, buf, t1, ad, lane);
             if (p + stride < A.npix) {
                 f_load_spec<P>(A.fft_in + (p + stride) * nf, lane, raw);
                 x_nyq_next = A.fft_in[(p + stride) * nf + N].x;
             }
-            f_core_pass23<P>(buf, t2, ad, lane);
+            f_core_pass23<P, PKB ? 2 : 0>(buf, t2, ad, lane);
         }
     };
     // spectrum stores (+ the inverse transform of the fused chain)
     auto part_b = [&]() {
         if constexpr (MODE != kInv) {
             int keep_lo = 0, keep_n = kFKeepAll;  // MODE == kPipe: this trace's keep range (every bin if it is not finite)
-            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND, KEEP>(
+            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND, KEEP, PKB>(
                 buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, p, A, lane, &sums, &keep_lo, &keep_n);
             if constexpr (MODE == kPipe) {
                 cx r[C1][R1];
@@ -1565,23 +1813,23 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
                     // f_inverse_input alone the kCfgLow builds spill 12-18 VGPRs, with the prefetch and passes 2-3 inside
                     // as well 38-43.
                     auto inverse = [&](auto low_tag) {
-                        f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP, decltype(low_tag)::value>(
+                        f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP, decltype(low_tag)::value, PKI>(
                             buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, lane, r, A.fft_out + p * nf,
                             4 - A.band_lo4, A.band_n + 4, THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
                         wave_sync();  // every lane has read Z before the core overwrites buf
-                        f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+                        f_core_pass1<P, TC, PKB>(r, buf, t1, ad, lane);
                     };
                     if (THZ_UNIFORM(keep_n) == kFKeepAll) inverse(FFalse{});
                     else inverse(FTrue{});
                 } else {
-                    f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
+                    f_inverse_input<P, true, CMASK, TC, true, BAND, KEEP, false, PKI>(buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s),
                                                                     mask_l, lane, r, A.fft_out + p * nf, 4 - A.band_lo4, A.band_n + 4,
                                                                     THZ_UNIFORM(keep_lo), THZ_UNIFORM(keep_n));
                     wave_sync();  // every lane has read Z before the core overwrites buf
-                    f_core_pass1<P, TC>(r, buf, t1, ad, lane);
+                    f_core_pass1<P, TC, PKB>(r, buf, t1, ad, lane);
                 }
                 if (p + stride < A.npix) f_load_raw<P>(A.in + (p + stride) * NT, lane, raw);
-                f_core_pass23<P>(buf, t2, ad, lane);
+                f_core_pass23<P, PKB ? 2 : 0>(buf, t2, ad, lane);
             }
         }
     };

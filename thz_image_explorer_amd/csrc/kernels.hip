@@ -1458,7 +1458,7 @@ __global__ __launch_bounds__(W * 64) THZ_WAVES_PER_SIMD(4) void k_dc_energy_edge
                 // 39 KiB a band moved through LDS (the kernel's bound beside its VALU work) 11.5 less
                 cx outv[R1];
                 f_core_pass1_regs<PL>(r, buf, tw1, ad);
-                f_core_pass23<PL, true, true>(buf, t2, ad, lane, &outv);
+                f_core_pass23<PL, 1, true>(buf, t2, ad, lane, &outv);
                 float acc = 0.0f;
 #pragma unroll
                 for (int j = 0; j < R1; ++j) {
@@ -2390,16 +2390,15 @@ static size_t f_grid(size_t npix)
     return g;
 }
 
-#ifdef THZ_EMU
-thread_local int g_f_last_cfg = -1;  // tests (the emulation harness): the kCfg bits of this thread's latest k_f launch
-#endif
+// tests (the emulation harness, and tests/test_gpu_cx_products.py through the library's symbol table): the kCfg bits of
+// this thread's latest fused (kPipe) k_f launch — a session's recompute follows that launch with a forward transform of
+// the mean trace, which is not recorded.  Not part of the C ABI of include/thzgpu.h.
+thread_local int g_f_last_cfg = -1;
 
 template <class PL, int MODE, int CFG>
 static void launch_f(hipStream_t st, const PlanDev &P, const FArgs &A)
 {
-#ifdef THZ_EMU
-    g_f_last_cfg = CFG;
-#endif
+    if constexpr (MODE == kPipe) g_f_last_cfg = CFG;
     const unsigned kBlock = f_block_threads<PL, CFG>();
     const size_t lds = PL::lds_bytes((int)(kBlock / kWave), CFG);
     const size_t g = f_grid<PL, MODE, CFG>(A.npix);
