@@ -498,6 +498,65 @@ int thz_optical_maps(thz_ctx *ctx, size_t npix, size_t nf, const float *d_amp, c
                      const float *d_thickness, float *d_n, float *d_alpha, float *d_kappa, int32_t *d_wraps,
                      float *d_slope);
 
+/* ------------------------------------------------------------------ */
+/* Echoes and layer thickness (K18)                     */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  A thickness is the delay between two pulses of one trace (front and back surface, coating
+ * layers: time-of-flight tomography) or of the pulse against the reference pulse (transmission); thz_peak_map finds one
+ * pulse only.  thz_echo_map is its multi-pulse form: the K strongest separated pulses of every trace.
+ *
+ * Per trace x[0 .. nt), with key as in thz_peak_map (mode 0 |x|, 1 x, 2 -x) and a NaN key ordered as -Inf:
+ *   rank 0      thz_peak_map's result by definition: the same index, offset and value, bit for bit, in every corner that
+ *               function defines (ties, NaNs, traces of -Inf).
+ *   candidates  for the ranks j >= 1: sample i is a candidate when its key is not NaN, i == 0 || key[i] > key[i-1], and
+ *               i == nt-1 || key[i] >= key[i+1].  A plateau gives its lowest index once; the shoulder of a pulse is
+ *               never a candidate, wherever the guard window ends.
+ *   threshold   thr = rel_threshold * key[index_0], one f32 product.  A candidate is admitted iff key >= thr (false when
+ *               thr is NaN).
+ *   rank j      (j = 1 .. K-1) the admitted candidate with the largest key among those with |i - index_m| >= guard for
+ *               every earlier rank m < j; of equal keys the lowest index.  If there is none, this rank and every later
+ *               one are absent: index -1, offset 0.0f, value 0.0f.
+ *   offset, value of a found rank follow thz_peak_map's rules around that index: the same f32 parabola through x, the
+ *               same clamp, the same exact-zero cases.
+ *   d_count     (npix) int32: the number of ranks found, at least 1.
+ * d_index (int32), d_offset, d_value (f32) are (K, npix), rank-major, in the way the optical maps are band-major.  Any
+ * output may be NULL.  One wave per trace and one read of the cube from HBM: the rounds behind the first work on what
+ * the wave holds in registers (traces of up to 4099 samples) or read the trace again through the cache; d_data needs
+ * 4-byte alignment only.  THZ_ERR_INVALID before any launch for a mode outside 0..2, K outside 1..THZ_ECHO_MAX,
+ * guard < 1, a threshold that is negative or not finite, nt == 0 or nt > 2^30.  npix == 0 is a no-op.  Time under
+ * THZ_STAGE_ECHO. */
+#define THZ_ECHO_MAX 4
+typedef struct thz_echo_cfg {
+    int32_t mode;         /* thz_peak_map's key: 0 |x|, 1 x, 2 -x */
+    int32_t n_echoes;     /* K, 1 .. THZ_ECHO_MAX */
+    int32_t guard;        /* >= 1: two reported pulses are at least this many samples apart */
+    float rel_threshold;  /* finite, >= 0 */
+} thz_echo_cfg;
+int thz_echo_map(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data, const thz_echo_cfg *cfg,
+                 int32_t *d_index, float *d_offset, float *d_value, int32_t *d_count);
+
+/* Delays and thicknesses from the (n_echoes, npix) index and offset maps of thz_echo_map.
+ *   mode 0  per pixel the found ranks (index >= 0) are put in ascending index order; for l = 0 .. K-2
+ *             delay[l] = (float)(i_{l+1} - i_l) + (o_{l+1} - o_l)   (int32 and f32 subtractions as written)
+ *             thickness[l] = scale[l] * delay[l]
+ *           and a layer whose later pulse is absent gets NaN in both.  Outputs (K-1, npix); K = 1 is THZ_ERR_INVALID.
+ *   mode 1  one row: delay = (float)(i_0 - ref_index) + (o_0 - ref_offset), thickness = scale[0] * delay.
+ * Either output may be NULL.  npix == 0 is a no-op.  Time under THZ_STAGE_ECHO. */
+typedef struct thz_layer_cfg {
+    int32_t mode;       /* 0: between consecutive pulses in TIME order; 1: rank 0 against a fixed arrival */
+    float scale[4];     /* mm per sample of delay, per layer: reflection c dt / (2 n_l), transmission c dt / (n - 1) */
+    int32_t ref_index;  /* mode 1: where the reference pulse peaks ... */
+    float ref_offset;   /* ... and its sub-sample offset (thz_host_echo_trace on the reference pulse) */
+} thz_layer_cfg;
+int thz_layer_map(thz_ctx *ctx, size_t npix, int n_echoes, const int32_t *d_index, const float *d_offset,
+                  const thz_layer_cfg *cfg, float *d_thickness, float *d_delay);
+
+/* thz_echo_map's selection for one host vector: index, offset, value hold cfg->n_echoes entries each, count one.  No
+ * GPU and no context: what gives ref_index / ref_offset from the reference pulse (thz_reference_spectrum's
+ * reference_out).  THZ_ERR_INVALID for the configurations thz_echo_map refuses. */
+int thz_host_echo_trace(const float *x, size_t nt, const thz_echo_cfg *cfg, int32_t *index, float *offset,
+                        float *value, int32_t *count);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -590,7 +649,13 @@ enum {
     THZ_BUF_OPT_ALPHA = 14,   /* likewise */
     THZ_BUF_OPT_KAPPA = 15,   /* likewise */
     THZ_BUF_OPT_WRAPS = 16,   /* (npix) int32 */
-    THZ_BUF_OPT_SLOPE = 17    /* (npix) f32 */
+    THZ_BUF_OPT_SLOPE = 17,   /* (npix) f32 */
+    THZ_BUF_ECHO_INDEX = 18,  /* (n_echoes, npix) int32 of the last thz_session_echo_map, rank-major */
+    THZ_BUF_ECHO_OFFSET = 19, /* (n_echoes, npix) f32 */
+    THZ_BUF_ECHO_VALUE = 20,  /* (n_echoes, npix) f32 */
+    THZ_BUF_ECHO_COUNT = 21,  /* (npix) int32 */
+    THZ_BUF_LAYER_THICKNESS = 22, /* (rows, npix) f32 of the last thz_session_layer_map */
+    THZ_BUF_LAYER_DELAY = 23  /* likewise */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -702,9 +767,23 @@ int thz_session_estimate_tilt(thz_session *s, int which, int mode, float rel_thr
  * thz_session_download; absent until the first call, and again after an upload).  For the three band-major ones the
  * pix0 / npix of thz_session_download count over the flattened (band, pixel) array of the last call.
  * A group has no form of its own: call this on thz_group_session_member(gs, i) with that slab's rows of the thickness
- * image; every pixel is independent, so the slabs' maps are the whole grid's rows. */
+ * image; every pixel is independent, so the slabs' maps are the whole grid's rows.
+ * A row of THZ_BUF_LAYER_THICKNESS (thz_session_layer_map below), taken through thz_session_buffer, is a valid
+ * d_thickness when the echo map was taken on this grid: the thickness image never leaves the device. */
 int thz_session_optical_maps(thz_session *s, const float *ref_amp, const float *ref_phase, size_t nf,
                              const thz_optical_cfg *cfg, const float *d_thickness);
+
+/* thz_echo_map on a resident cube: `which` = THZ_BUF_RAW or THZ_BUF_DATA exactly as for thz_session_peak_map (the same
+ * grids, the same THZ_ERR_NOT_READY and THZ_ERR_INVALID cases).  Fills the four resident images THZ_BUF_ECHO_INDEX /
+ * _OFFSET / _VALUE / _COUNT (thz_session_buffer, thz_session_download; absent until the first call, and again after an
+ * upload).  For the three rank-major ones the pix0 / npix of thz_session_download count over the flattened (rank, pixel)
+ * array of the last call.
+ * thz_session_layer_map runs thz_layer_map on the last echo map (THZ_ERR_NOT_READY when there is none) and fills
+ * THZ_BUF_LAYER_THICKNESS / _DELAY, (K - 1, npix) in mode 0 and (1, npix) in mode 1, with the same download rule.
+ * A group has no form of its own: call these on thz_group_session_member(gs, i); every pixel is independent, so the
+ * slabs' maps are the whole grid's rows. */
+int thz_session_echo_map(thz_session *s, int which, const thz_echo_cfg *cfg);
+int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */
@@ -953,7 +1032,8 @@ enum {
     THZ_STAGE_PROBE = 11,
     THZ_STAGE_PEAK = 12,
     THZ_STAGE_OPTICAL = 13,
-    THZ_STAGE_COUNT = 14
+    THZ_STAGE_ECHO = 14,
+    THZ_STAGE_COUNT = 15
 };
 /* hipEvent bracketing of every stage call on the context's stream.
  *   0  off (default)

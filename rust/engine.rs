@@ -86,6 +86,10 @@ pub struct GpuEngine {
     /// (uuid, polygon) of the ifft stage's regions, in the order the device holds them
     rois: Vec<(String, Polygon)>,
     rois_dirty: bool,
+    /// the last `echo_map`: rows per local member, columns and ranks (0: none)
+    echo_rows: Vec<usize>,
+    echo_gy: usize,
+    echo_k: usize,
 }
 
 // the raw handles are only touched under the Mutex around the engine
@@ -105,7 +109,7 @@ impl GpuEngine {
         pending.scale_factor = 1;
         pending.want_means = 1;
         GpuEngine { group, session: ptr::null_mut(), pending, dirty_from: 1, nx: 0, ny: 0, nt: 0, fd_real: vec![], fd_cmask: vec![],
-                    plugins_dirty: true, rois: vec![], rois_dirty: false }
+                    plugins_dirty: true, rois: vec![], rois_dirty: false, echo_rows: vec![], echo_gy: 0, echo_k: 0 }
     }
 
     pub fn available(&self) -> bool { !self.group.is_null() }
@@ -406,6 +410,88 @@ impl GpuEngine {
                 at += mine;
             }
             Some((n, alpha, kappa, wraps, slope, gx, gy))
+        }
+    }
+
+    /// The `cfg.n_echoes` strongest separated pulses of every trace this process holds (`thz_session_echo_map` on each
+    /// local member, slab after slab: every pixel is independent), of the raw cube (`which = THZ_BUF_RAW`) or of the
+    /// chain's final traces (`THZ_BUF_DATA`; whatever the walk has recorded is flushed first).
+    /// -> (index, offset, value: (n_echoes, gx, gy), rank-major with index -1 for a rank that was not found;
+    /// count: (gx, gy); gx; gy)
+    pub fn echo_map(&mut self, which: c_int, cfg: &ThzEchoCfg) -> Option<(Vec<i32>, Vec<f32>, Vec<f32>, Vec<i32>, usize, usize)> {
+        self.echo_k = 0;
+        if self.session.is_null() || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) { return None; }
+        if which == THZ_BUF_DATA && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            self.echo_rows = vec![0usize; members as usize];
+            let (mut gx, mut gy) = (0usize, 0usize);
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                if thz_session_echo_map(s, which, cfg) != THZ_OK { return None; }
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut self.echo_rows[i as usize]);
+                    gy = self.ny;
+                } else {
+                    thz_session_grid(s, &mut self.echo_rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                }
+                gx += self.echo_rows[i as usize];
+            }
+            let (k, npix) = (cfg.n_echoes as usize, gx * gy);
+            let (mut index, mut offset, mut value, mut count) = (vec![-1i32; k * npix], vec![0f32; k * npix], vec![0f32; k * npix], vec![0i32; npix]);
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = self.echo_rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                for j in 0..k { // a member's maps are rank-major over ITS pixels
+                    if thz_session_download(s, THZ_BUF_ECHO_INDEX, j * mine, mine, index.as_mut_ptr().add(j * npix + at) as *mut c_void) != THZ_OK
+                        || thz_session_download(s, THZ_BUF_ECHO_OFFSET, j * mine, mine, offset.as_mut_ptr().add(j * npix + at) as *mut c_void) != THZ_OK
+                        || thz_session_download(s, THZ_BUF_ECHO_VALUE, j * mine, mine, value.as_mut_ptr().add(j * npix + at) as *mut c_void) != THZ_OK {
+                        return None;
+                    }
+                }
+                if thz_session_download(s, THZ_BUF_ECHO_COUNT, 0, mine, count.as_mut_ptr().add(at) as *mut c_void) != THZ_OK { return None; }
+                at += mine;
+            }
+            self.echo_gy = gy;
+            self.echo_k = k;
+            Some((index, offset, value, count, gx, gy))
+        }
+    }
+
+    /// Delays and thicknesses from the last `echo_map` (`thz_session_layer_map` on each local member): (rows, gx, gy)
+    /// with rows = n_echoes - 1 between consecutive pulses (`cfg.mode` 0) and 1 against a fixed arrival (`cfg.mode` 1).
+    /// A member's `THZ_BUF_LAYER_THICKNESS` stays resident: a row of it is a valid `d_thickness` of
+    /// `thz_session_optical_maps`.  -> (thickness, delay, rows, gx, gy)
+    pub fn layer_map(&mut self, cfg: &ThzLayerCfg) -> Option<(Vec<f32>, Vec<f32>, usize, usize, usize)> {
+        if self.session.is_null() || self.echo_k == 0 || (cfg.mode == 0 && self.echo_k < 2) { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            if members as usize != self.echo_rows.len() { return None; }
+            for i in 0..members {
+                if thz_session_layer_map(thz_group_session_member(self.session, i), cfg) != THZ_OK { return None; }
+            }
+            let rows = if cfg.mode == 0 { self.echo_k - 1 } else { 1 };
+            let gy = self.echo_gy;
+            let gx: usize = self.echo_rows.iter().sum();
+            let npix = gx * gy;
+            let (mut thickness, mut delay) = (vec![0f32; rows * npix], vec![0f32; rows * npix]);
+            let mut at = 0usize;
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = self.echo_rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                for l in 0..rows {
+                    if thz_session_download(s, THZ_BUF_LAYER_THICKNESS, l * mine, mine, thickness.as_mut_ptr().add(l * npix + at) as *mut c_void) != THZ_OK
+                        || thz_session_download(s, THZ_BUF_LAYER_DELAY, l * mine, mine, delay.as_mut_ptr().add(l * npix + at) as *mut c_void) != THZ_OK {
+                        return None;
+                    }
+                }
+                at += mine;
+            }
+            Some((thickness, delay, rows, gx, gy))
         }
     }
 

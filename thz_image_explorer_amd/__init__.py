@@ -13,5 +13,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       host_optical_properties, host_align_reference, PlotOut, host_gaussian_kernel1d, host_select_step, host_select_value,
                       TiltFit, host_arrival_plane_fit, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, PEAK_ABS, PEAK_MAX, PEAK_MIN,
                       OpticalCfg, optical_cfg, OPTICAL_MAX_BANDS, STAGE_OPTICAL, BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA,
-                      BUF_OPT_WRAPS, BUF_OPT_SLOPE)
+                      BUF_OPT_WRAPS, BUF_OPT_SLOPE,
+                      EchoCfg, LayerCfg, echo_cfg, layer_cfg, host_echo_trace, ECHO_MAX, LAYER_BETWEEN, LAYER_REFERENCE, STAGE_ECHO,
+                      BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY)
 from . import binding  # noqa: F401

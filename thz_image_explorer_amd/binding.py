@@ -22,7 +22,7 @@ STATUS = {0: "THZ_OK", -1: "THZ_ERR_INVALID", -2: "THZ_ERR_UNSUPPORTED", -3: "TH
 WIN_ADAPTED_BLACKMAN, WIN_BLACKMAN, WIN_HANNING, WIN_HAMMING, WIN_FLAT_TOP = range(5)
 STAGE_FFT, STAGE_FD_MASK, STAGE_IFFT, STAGE_PIPELINE, STAGE_TD_WINDOW, STAGE_INTENSITY, \
     STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE, STAGE_PEAK, \
-    STAGE_OPTICAL = range(14)
+    STAGE_OPTICAL, STAGE_ECHO = range(15)
 PEAK_ABS, PEAK_MAX, PEAK_MIN = range(3)  # thz_peak_map's mode: largest |x|, maximum, minimum
 
 
@@ -116,8 +116,11 @@ class PlotOut(C.Structure):
 
 BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BUF_AVG_AMPLITUDES, \
     BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, \
-    BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE = range(18)
+    BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE, \
+    BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY = range(24)
 OPTICAL_MAX_BANDS = 8
+ECHO_MAX = 4
+LAYER_BETWEEN, LAYER_REFERENCE = range(2)  # thz_layer_map's mode: consecutive pulses, rank 0 against a fixed arrival
 
 
 class TiltFit(C.Structure):
@@ -144,6 +147,27 @@ def optical_cfg(thickness, anchor, bands) -> OpticalCfg:
     cfg.n_bands = len(bands)
     for i, (k0, k1) in enumerate(list(bands)[:OPTICAL_MAX_BANDS]):
         cfg.band_k0[i], cfg.band_k1[i] = int(k0), int(k1)
+    return cfg
+
+
+class EchoCfg(C.Structure):
+    """thz_echo_cfg: key, number of ranks, guard distance and relative threshold of thz_echo_map"""
+    _fields_ = [("mode", C.c_int32), ("n_echoes", C.c_int32), ("guard", C.c_int32), ("rel_threshold", C.c_float)]
+
+
+class LayerCfg(C.Structure):
+    """thz_layer_cfg: what thz_layer_map takes the delays between, and the mm per sample of every layer"""
+    _fields_ = [("mode", C.c_int32), ("scale", C.c_float * 4), ("ref_index", C.c_int32), ("ref_offset", C.c_float)]
+
+
+def echo_cfg(mode=PEAK_MAX, n_echoes=2, guard=30, rel_threshold=0.2) -> EchoCfg:
+    return EchoCfg(int(mode), int(n_echoes), int(guard), float(rel_threshold))
+
+
+def layer_cfg(mode=LAYER_BETWEEN, scale=(1.0,), ref_index=0, ref_offset=0.0) -> LayerCfg:
+    """scale: mm per sample of delay for each layer; a shorter list is continued with its last value"""
+    sc = [float(v) for v in np.atleast_1d(scale)][:4]
+    cfg = LayerCfg(int(mode), (C.c_float * 4)(*(sc + [sc[-1]] * (4 - len(sc)))), int(ref_index), float(ref_offset))
     return cfg
 
 
@@ -264,6 +288,11 @@ SYMBOLS = [
     ("thz_group_session_peak_result", _P, [_P, C.c_int]),
     ("thz_optical_maps", C.c_int, [_P, _SZ, _SZ, _P, _P, _P, _P, _P, C.POINTER(OpticalCfg), _P, _P, _P, _P, _P, _P]),
     ("thz_session_optical_maps", C.c_int, [_P, _P, _P, _SZ, C.POINTER(OpticalCfg), _P]),
+    ("thz_echo_map", C.c_int, [_P, _SZ, _SZ, _P, C.POINTER(EchoCfg), _P, _P, _P, _P]),
+    ("thz_layer_map", C.c_int, [_P, _SZ, C.c_int, _P, _P, C.POINTER(LayerCfg), _P, _P]),
+    ("thz_host_echo_trace", C.c_int, [_P, _SZ, C.POINTER(EchoCfg), _P, _P, _P, _P]),
+    ("thz_session_echo_map", C.c_int, [_P, C.c_int, C.POINTER(EchoCfg)]),
+    ("thz_session_layer_map", C.c_int, [_P, C.POINTER(LayerCfg)]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -442,6 +471,17 @@ def host_arrival_plane_fit(moments):
     return rc, fit
 
 
+def host_echo_trace(x, cfg: EchoCfg):
+    """thz_echo_map's selection for one host vector -> (index int32, offset f32, value f32: n_echoes each; count)"""
+    a = np.ascontiguousarray(x, np.float32).ravel()
+    k = max(int(cfg.n_echoes), 1)
+    idx, off, val = np.full(k, -2, np.int32), np.zeros(k, np.float32), np.zeros(k, np.float32)
+    n = C.c_int32()
+    _rc(load_library().thz_host_echo_trace(a.ctypes.data, a.size, C.byref(cfg), idx.ctypes.data, off.ctypes.data,
+                                           val.ctypes.data, C.byref(n)), "thz_host_echo_trace")
+    return idx, off, val, n.value
+
+
 def voxel_cfg_default() -> VoxelCfg:
     cfg = VoxelCfg()
     _rc(load_library().thz_voxel_cfg_default(C.byref(cfg)), "voxel_cfg_default")
@@ -607,6 +647,24 @@ class Session:
         return (*bands, self.download(BUF_OPT_WRAPS, npix=gx * gy).reshape(gx, gy),
                 self.download(BUF_OPT_SLOPE, npix=gx * gy).reshape(gx, gy))
 
+    def echo_map(self, which, cfg: "EchoCfg"):
+        """thz_session_echo_map of THZ_BUF_RAW / THZ_BUF_DATA -> (index int32, offset f32, value f32: (n_echoes, gx, gy);
+        count int32 (gx, gy))"""
+        self.eng._check(self.eng.lib.thz_session_echo_map(self.h, int(which), C.byref(cfg)))
+        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        k = int(cfg.n_echoes)
+        self._echo_grid = (k, gx, gy)
+        return (*(self.download(b, npix=k * gx * gy).reshape(k, gx, gy) for b in (BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE)),
+                self.download(BUF_ECHO_COUNT, npix=gx * gy).reshape(gx, gy))
+
+    def layer_map(self, cfg: "LayerCfg"):
+        """thz_session_layer_map on the last echo_map -> (thickness, delay), each (rows, gx, gy) f32: rows = n_echoes - 1
+        between consecutive pulses, 1 against a fixed arrival"""
+        self.eng._check(self.eng.lib.thz_session_layer_map(self.h, C.byref(cfg)))
+        k, gx, gy = self._echo_grid
+        rows = k - 1 if cfg.mode == LAYER_BETWEEN else 1
+        return tuple(self.download(b, npix=rows * gx * gy).reshape(rows, gx, gy) for b in (BUF_LAYER_THICKNESS, BUF_LAYER_DELAY))
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -628,6 +686,8 @@ class Session:
             out = np.empty(npix, np.int32 if which == BUF_PEAK_INDEX else np.float32)
         elif BUF_OPT_N <= which <= BUF_OPT_SLOPE:  # npix: entries of the last call's (band, pixel) array, from the caller
             out = np.empty(npix, np.int32 if which == BUF_OPT_WRAPS else np.float32)
+        elif BUF_ECHO_INDEX <= which <= BUF_LAYER_DELAY:  # npix: entries of the last call's (row, pixel) array, likewise
+            out = np.empty(npix, np.int32 if which in (BUF_ECHO_INDEX, BUF_ECHO_COUNT) else np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -993,6 +1053,17 @@ class Engine:
             raise ValueError("ref_amp, ref_phase and freq hold nf values each")
         self._check(self.lib.thz_optical_maps(self.ctx, npix, nf, _dp(amp), _dp(phase), *[h.ctypes.data for h in host],
                                               C.byref(cfg), _dp(thickness), _dp(n), _dp(alpha), _dp(kappa), _dp(wraps), _dp(slope)))
+
+    def echo_map(self, npix, nt, data, cfg: "EchoCfg", index=None, offset=None, value=None, count=None):
+        """thz_echo_map: data (npix, nt); index, offset, value (n_echoes, npix) and count (npix) are device pointers /
+        DevBufs or None"""
+        self._check(self.lib.thz_echo_map(self.ctx, npix, nt, _dp(data), C.byref(cfg), _dp(index), _dp(offset), _dp(value),
+                                          _dp(count)))
+
+    def layer_map(self, npix, n_echoes, index, offset, cfg: "LayerCfg", thickness=None, delay=None):
+        """thz_layer_map: index, offset (n_echoes, npix) -> thickness, delay (n_echoes - 1 or 1, npix), all on the device"""
+        self._check(self.lib.thz_layer_map(self.ctx, npix, int(n_echoes), _dp(index), _dp(offset), C.byref(cfg), _dp(thickness),
+                                           _dp(delay)))
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

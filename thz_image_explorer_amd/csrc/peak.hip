@@ -18,40 +18,6 @@
 
 namespace thz {
 
-namespace {
-
-// A key's bits mapped so that unsigned order is the floats' order (-0 counted as +0) and no number maps to 0: 0 is
-// "no candidate", what a lane that saw nothing above -Inf hands in.  The wave's winner is then two maxima — of the
-// mapped keys, and among the lanes that hold that key of the complemented indices (the LOWEST index is the largest) —
-// and a maximum does not depend on which lane held what.
-__device__ __forceinline__ unsigned peak_ordered(float key, bool have)
-{
-    unsigned b = __builtin_bit_cast(unsigned, key);
-    if (b == 0x80000000u) b = 0u;
-    const unsigned ordered = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // -Inf -> 0x007fffff, the smallest
-    return have ? ordered : 0u;
-}
-
-template <int MODE>
-__device__ __forceinline__ float peak_key(float x)
-{
-    return MODE == 0 ? fabsf(x) : (MODE == 1 ? x : -x);
-}
-
-// A lane walks its own samples in ascending order, so `>` alone keeps the lowest index of equal keys; a NaN key compares
-// false and never wins.  Neither does a key of -Inf against the initial -Inf: a trace that holds nothing above -Inf is
-// settled on the cold path of the kernel.
-template <int MODE>
-__device__ __forceinline__ void peak_take(float x, int i, float &best, int &best_i)
-{
-    const float key = peak_key<MODE>(x);
-    const bool take = key > best;
-    best = take ? key : best;
-    best_i = take ? i : best_i;
-}
-
-}  // namespace
-
 // kPeakBatch: 16-byte loads a lane has in flight before it looks at the first.  Measured at 1, 2, 4, 8 and 16 on
 // 512 x 512 x 1001 and 1024 x 1024 x 4096 (profiles/peak_map_timing.txt): 2 is the fastest or level with the fastest at
 // both; larger batches cost registers and, on short traces, loads of the last quad over again.
@@ -89,31 +55,11 @@ __global__ __launch_bounds__(256) void k_peak_map(size_t npix, int nt, const flo
         }
         // the nt % 4 samples behind the last whole quad: above every index the lane has seen
         if (nt4 + lane < nt) peak_take<MODE>(x[nt4 + lane], nt4 + lane, best, best_i);
-        const unsigned mine = peak_ordered(best, best_i >= 0);
-        const unsigned top = wave_reduce_max_u32(mine);
-        int k = (int)(0xffffffffu - wave_reduce_max_u32(mine == top ? 0xffffffffu - (unsigned)best_i : 0u));
-        if (top == 0u) {
-            // (wave-uniform, cold) no key above -Inf: the first sample that is a number — its key is -Inf, a tie of all
-            // such samples — or, in a trace of NaNs, sample 0
-            unsigned first = 0u;  // 0xffffffff - index of the lane's first number (never 0); 0: none
-            for (int i = lane; i < nt; i += kWave) {
-                const float key = peak_key<MODE>(x[i]);
-                if (key == key && first == 0u) first = 0xffffffffu - (unsigned)i;
-            }
-            first = wave_reduce_max_u32(first);
-            k = first ? (int)(0xffffffffu - first) : 0;
-        }
+        int k = peak_wave_winner(best, best_i);
+        if (k < 0) k = peak_first_number<MODE>(x, nt, lane);  // (wave-uniform, cold) no key above -Inf
         if (lane == 0) {
-            // the winner and its neighbours again (the trace has just passed through the cache), as three loads that do
-            // not wait for each other: at the trace's ends a neighbour's place is taken by the winner itself, unused
-            const bool inner = k > 0 && k < nt - 1;
-            const float y0 = x[k], ym = x[inner ? k - 1 : k], yp = x[inner ? k + 1 : k];
-            float off = 0.0f;
-            const float den = ym - 2.0f * y0 + yp;
-            if (inner && isfinite(ym) && isfinite(y0) && isfinite(yp) && den != 0.0f) {
-                off = 0.5f * (ym - yp) / den;
-                off = isfinite(off) ? fminf(fmaxf(off, -0.5f), 0.5f) : 0.0f;
-            }
+            float y0;
+            const float off = peak_vertex(x, k, nt, y0);
             if (index) index[p] = k;
             if (offset) offset[p] = off;
             if (value) value[p] = y0;

@@ -66,6 +66,15 @@ struct thz_session {
     int32_t *d_opt_wraps = nullptr;
     size_t opt_floats = 0, opt_wraps_cap = 0;  // allocated
     size_t opt_pix = 0, opt_bands = 0;         // pixels and bands of the last call; 0 pixels: the maps are absent
+    // echo maps of the last thz_session_echo_map (echo_api.cpp), four bytes an entry:
+    // d_echo = [index | offset | value: (echo_k, echo_pix) each, rank-major | count: echo_pix]
+    float *d_echo = nullptr;
+    size_t echo_cap = 0;                       // entries allocated
+    size_t echo_pix = 0, echo_k = 0;           // pixels and ranks of the last call; 0 pixels: the maps are absent
+    // ... and what the last thz_session_layer_map made of them: d_layer = [thickness | delay: (layer_rows, layer_pix) each]
+    float *d_layer = nullptr;
+    size_t layer_cap = 0;
+    size_t layer_pix = 0, layer_rows = 0;
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;

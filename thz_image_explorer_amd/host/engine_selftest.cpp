@@ -267,6 +267,33 @@ int main(int argc, char **argv)
             std::printf("optical_maps: slope over two slabs against one, largest difference %.3g rad / bin\n", worst);
             CHECK(worst < 1e-4, "optical_maps over two slabs == over one (slope)");
         }
+        {
+            // echo maps and layer maps of the raw cube, on one slab and on two: every pixel is independent and the
+            // winners depend on the data alone, so the slabs' maps are the whole grid's rows bit for bit
+            thz_echo_cfg ec{};
+            ec.mode = 1; ec.n_echoes = 3; ec.guard = 10; ec.rel_threshold = 0.1f;
+            std::vector<int32_t> i1, i2, c1, c2;
+            std::vector<float> o1, o2, v1, v2, t1, t2, d1, d2;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0, r1 = 0, r2 = 0;
+            CHECK(eng.echo_map(THZ_BUF_RAW, ec, i1, o1, v1, c1, gx1, gy1), "echo_map on one slab");
+            CHECK(eng2.echo_map(THZ_BUF_RAW, ec, i2, o2, v2, c2, gx2, gy2), "echo_map on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1, "echo_map: the whole grid");
+            CHECK(i1.size() == 3 * gx1 * gy1 && c1.size() == gx1 * gy1, "echo_map: sizes");
+            CHECK(i1 == i2 && c1 == c2 && std::memcmp(o1.data(), o2.data(), o1.size() * sizeof(float)) == 0
+                      && std::memcmp(v1.data(), v2.data(), v1.size() * sizeof(float)) == 0,
+                  "echo_map over two slabs == over one");
+            size_t seconds = 0;
+            for (int32_t n : c1) seconds += n >= 2;
+            std::printf("echo_map: %zu of %zu pixels with a second pulse\n", seconds, c1.size());
+            thz_layer_cfg lc{};
+            lc.mode = 0;
+            lc.scale[0] = lc.scale[1] = 0.01f;
+            CHECK(eng.layer_map(lc, t1, d1, r1, gx1, gy1) && eng2.layer_map(lc, t2, d2, r2, gx2, gy2), "layer_map on one slab and on two");
+            CHECK(r1 == 2 && r2 == 2 && t1.size() == 2 * gx1 * gy1 && t2.size() == t1.size(), "layer_map: sizes");
+            CHECK(std::memcmp(t1.data(), t2.data(), t1.size() * sizeof(float)) == 0
+                      && std::memcmp(d1.data(), d2.data(), d1.size() * sizeof(float)) == 0,
+                  "layer_map over two slabs == over one");
+        }
         small_bank(q.filter_by("Deconvolution"));
         q.filters_active[q.filter_chain[q.index_of("Deconvolution")]] = true;
         q.update_filter(q.index_of("Deconvolution"));

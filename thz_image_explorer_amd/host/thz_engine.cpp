@@ -395,6 +395,79 @@ bool GpuEngine::optical_maps(const std::vector<float> &ref_amp, const std::vecto
     }
     return true;
 }
+bool GpuEngine::echo_map(int which, const thz_echo_cfg &cfg, std::vector<int32_t> &index, std::vector<float> &offset,
+                         std::vector<float> &value, std::vector<int32_t> &count, size_t &gx, size_t &gy)
+{
+    gx = gy = 0;
+    echo_k_ = 0;
+    if (!session_ || (which != THZ_BUF_RAW && which != THZ_BUF_DATA)) return false;
+    if (which == THZ_BUF_DATA && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    echo_rows_.assign((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        if (thz_session_echo_map(s, which, &cfg) != THZ_OK) return false;
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &echo_rows_[(size_t)i]);
+            gy = ny;
+        } else {
+            thz_session_grid(s, &echo_rows_[(size_t)i], &gy, nullptr, nullptr);
+        }
+        gx += echo_rows_[(size_t)i];
+    }
+    const size_t K = (size_t)cfg.n_echoes, npix = gx * gy;
+    index.assign(K * npix, -1);
+    offset.assign(K * npix, 0.0f);
+    value.assign(K * npix, 0.0f);
+    count.assign(npix, 0);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = echo_rows_[(size_t)i] * gy;
+        if (!mine) continue;
+        for (size_t j = 0; j < K; ++j) {  // a member's maps are rank-major over ITS pixels
+            if (thz_session_download(s, THZ_BUF_ECHO_INDEX, j * mine, mine, index.data() + j * npix + at) != THZ_OK
+                || thz_session_download(s, THZ_BUF_ECHO_OFFSET, j * mine, mine, offset.data() + j * npix + at) != THZ_OK
+                || thz_session_download(s, THZ_BUF_ECHO_VALUE, j * mine, mine, value.data() + j * npix + at) != THZ_OK)
+                return false;
+        }
+        if (thz_session_download(s, THZ_BUF_ECHO_COUNT, 0, mine, count.data() + at) != THZ_OK) return false;
+        at += mine;
+    }
+    echo_gy_ = gy;
+    echo_k_ = K;
+    return true;
+}
+bool GpuEngine::layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,
+                          size_t &gx, size_t &gy)
+{
+    rows = gx = gy = 0;
+    if (!session_ || !echo_k_ || (cfg.mode == 0 && echo_k_ < 2)) return false;
+    const int members = thz_group_local_count(group_);
+    if ((size_t)members != echo_rows_.size()) return false;
+    for (int i = 0; i < members; ++i)
+        if (thz_session_layer_map(thz_group_session_member(session_, i), &cfg) != THZ_OK) return false;
+    rows = cfg.mode == 0 ? echo_k_ - 1 : 1;
+    gy = echo_gy_;
+    for (size_t r : echo_rows_) gx += r;
+    const size_t npix = gx * gy;
+    thickness.assign(rows * npix, 0.0f);
+    delay.assign(rows * npix, 0.0f);
+    size_t at = 0;
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = echo_rows_[(size_t)i] * gy;
+        if (!mine) continue;
+        for (size_t l = 0; l < rows; ++l) {
+            if (thz_session_download(s, THZ_BUF_LAYER_THICKNESS, l * mine, mine, thickness.data() + l * npix + at) != THZ_OK
+                || thz_session_download(s, THZ_BUF_LAYER_DELAY, l * mine, mine, delay.data() + l * npix + at) != THZ_OK)
+                return false;
+        }
+        at += mine;
+    }
+    return true;
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;

@@ -80,6 +80,17 @@ public:
     bool optical_maps(const std::vector<float> &ref_amp, const std::vector<float> &ref_phase, const thz_optical_cfg &cfg,
                       std::vector<float> &n, std::vector<float> &alpha, std::vector<float> &kappa, std::vector<int32_t> &wraps,
                       std::vector<float> &slope, size_t &gx, size_t &gy);
+    // The cfg.n_echoes strongest separated pulses of every trace this process holds (thz_session_echo_map on each local
+    // member, slab after slab: every pixel is independent), of the raw cube (which = THZ_BUF_RAW) or of the chain's final
+    // traces (THZ_BUF_DATA; whatever the walk has recorded is flushed first).
+    // index, offset, value: (n_echoes, gx, gy), rank-major with index -1 for a rank that was not found; count: (gx, gy)
+    bool echo_map(int which, const thz_echo_cfg &cfg, std::vector<int32_t> &index, std::vector<float> &offset,
+                  std::vector<float> &value, std::vector<int32_t> &count, size_t &gx, size_t &gy);
+    // Delays and thicknesses from the last echo_map (thz_session_layer_map on each local member): (rows, gx, gy) with
+    // rows = n_echoes - 1 between consecutive pulses (cfg.mode 0) and 1 against a fixed arrival (cfg.mode 1).  A member's
+    // THZ_BUF_LAYER_THICKNESS stays resident: a row of it is a valid d_thickness of thz_session_optical_maps
+    bool layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,
+                   size_t &gx, size_t &gy);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
@@ -95,6 +106,8 @@ private:
     int dirty_from_ = 1;
     std::vector<float> fd_real_, fd_cmask_;  // empty = that plugin is off
     bool plugins_dirty_ = true;
+    std::vector<size_t> echo_rows_;          // the last echo_map: rows per local member, columns and ranks (0: none)
+    size_t echo_gy_ = 0, echo_k_ = 0;
     std::vector<std::pair<std::string, Polygon>> rois_;
     bool rois_dirty_ = false;
 };
