@@ -557,6 +557,52 @@ int thz_layer_map(thz_ctx *ctx, size_t npix, int n_echoes, const int32_t *d_inde
 int thz_host_echo_trace(const float *x, size_t nt, const thz_echo_cfg *cfg, int32_t *index, float *offset,
                         float *value, int32_t *count);
 
+/* ------------------------------------------------------------------ */
+/* Principal components of a scan (K19)                 */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  "Which pixels have a different spectrum at all?" is principal component analysis of the
+ * spectra: the mean spectrum, the covariance of the columns over the pixels, its leading eigenvectors (the components)
+ * and one score image per component.  Four calls that compose; the outputs of the first two are plain sums, so the
+ * slabs of a group are added on the host.
+ *
+ * Every device call sees an (npix x L) f32 matrix X[p, j] = d_x[p * row_stride + j * col_step] (both in floats,
+ * col_step >= 1, 4-byte alignment only: rows of the resident cubes are never 16-byte aligned), 1 <= L <=
+ * THZ_PCA_MAX_LEN, and an optional d_mask: npix uint8 in the cube's own pixel order (not thz_roi_mask's swapped
+ * coordinates), NULL for none.  A pixel with mask 0 is left out of the sums and of the Gram matrix; it still gets
+ * scores.  Anything outside these limits, or a required pointer that is NULL, is THZ_ERR_INVALID before any launch or
+ * allocation; npix == 0 is a no-op that returns zeros.  NaN and Inf get no special case: they propagate.
+ *
+ *   thz_pca_sums    sum[j] = sum over the unmasked pixels of X[p, j], added in f64 in a fixed order; *count their number.
+ *   thz_pca_gram    gram[i * L + j] = sum_p a[p, i] * a[p, j] with a[p, j] = X[p, j] - mu[j], ONE f32 subtraction made when
+ *                   the element is loaded (a = X when mu is NULL; a masked pixel enters as a = 0).  32 x 32 tiles of the
+ *                   upper triangle over chunks of pixels on the exact-f32 matrix instruction (v_mfma_f32_32x32x2_f32, the
+ *                   pixel index is its k; a diagonal tile's two operands are the same registers), whose result is a
+ *                   k-ordered fmaf chain: one f32 accumulator takes at most THZ_PCA_CHAIN products before it is added
+ *                   into f64, and a second kernel adds the slabs' f64 partial tiles in slab order and writes the lower
+ *                   triangle as the mirror.  No floating-point atomics: the same inputs give the same bits on every
+ *                   run, gram is exactly symmetric, and |gram_ij - exact| <= (THZ_PCA_CHAIN + 2) 2^-24 sum_p |a_pi a_pj|.
+ *   thz_host_pca_components   plain C++ in f64, no GPU and no context (Householder tridiagonalisation + implicit QL):
+ *                   C = gram / (count - 1); the K largest eigenvalues in descending order; each eigenvector with unit
+ *                   2-norm, its sign chosen so that its entry of largest magnitude is positive (the lowest index wins a
+ *                   tie), then rounded to f32 into components (K x L); *total_variance = trace(C).  THZ_ERR_INVALID for
+ *                   count < 2, K outside 1 .. min(L, THZ_PCA_MAX_COMPONENTS), L outside 1 .. THZ_PCA_MAX_LEN, a
+ *                   non-finite entry, or an iteration that does not converge (it is bounded: the call always returns).
+ *   thz_pca_scores  d_scores[c * npix + p] = sum_j a[p, j] * components[c * L + j] in f32 for EVERY pixel, one wave per
+ *                   pixel: lane l adds j = l, l + 64, ... in ascending order, then the lanes as a fixed tree — the order
+ *                   depends on L alone.  mu (L host floats or NULL) and components (K x L host floats) go up once per call.
+ * Time of the gram and score launches under THZ_STAGE_PCA. */
+#define THZ_PCA_MAX_LEN 512
+#define THZ_PCA_MAX_COMPONENTS 8
+#define THZ_PCA_CHAIN 1024
+int thz_pca_sums(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
+                 const uint8_t *d_mask, double *sum /* L, host */, uint64_t *count);
+int thz_pca_gram(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
+                 const uint8_t *d_mask, const float *mu /* L host floats or NULL */, double *gram /* L x L, host */);
+int thz_host_pca_components(const double *gram, size_t L, uint64_t count, int K, float *components /* K x L */,
+                            double *eigenvalues /* K */, double *total_variance);
+int thz_pca_scores(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
+                   const float *mu, const float *components, int K, float *d_scores /* (K, npix) */);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -655,7 +701,10 @@ enum {
     THZ_BUF_ECHO_VALUE = 20,  /* (n_echoes, npix) f32 */
     THZ_BUF_ECHO_COUNT = 21,  /* (npix) int32 */
     THZ_BUF_LAYER_THICKNESS = 22, /* (rows, npix) f32 of the last thz_session_layer_map */
-    THZ_BUF_LAYER_DELAY = 23  /* likewise */
+    THZ_BUF_LAYER_DELAY = 23, /* likewise */
+    THZ_BUF_PCA_SCORES = 24,  /* (K, npix) f32 of the last thz_session_pca / _pca_project, component-major */
+    THZ_BUF_PCA_COMPONENTS = 25, /* (K, L) f32 */
+    THZ_BUF_PCA_MEAN = 26     /* (L) f32; zeros when the call did not centre */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -784,6 +833,42 @@ int thz_session_optical_maps(thz_session *s, const float *ref_amp, const float *
  * slabs' maps are the whole grid's rows. */
 int thz_session_echo_map(thz_session *s, int which, const thz_echo_cfg *cfg);
 int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg);
+
+/* Principal components of a resident cube.  `which` names the matrix: THZ_BUF_AMPLITUDES or THZ_BUF_PHASES (columns
+ * are bins, nf = nt_out / 2 + 1 of them), THZ_BUF_DATA (samples, nt_out) — all three on the last recompute's grid, as
+ * thz_session_peak_map and thz_session_optical_maps define it, THZ_ERR_NOT_READY before a recompute — or THZ_BUF_RAW
+ * (samples, nt, the raw grid).  THZ_BUF_FFT and anything else is THZ_ERR_INVALID.  Column j of the matrix is column
+ * first + j * step of the cube, j = 0 .. count-1: count in 1 .. THZ_PCA_MAX_LEN, step >= 1, the last one inside the
+ * row (THZ_ERR_INVALID).  d_mask: optional, one uint8 per pixel of that grid, on the session's device.
+ * The spectra are read in place through the session's own pointers: the next recompute still knows their zeros.
+ *
+ * thz_session_pca runs the four calls: thz_pca_sums; mu = (float)(sum / count) in f64 (center == 0: no mu is formed,
+ * the Gram matrix is taken of X itself and THZ_BUF_PCA_MEAN holds zeros); thz_pca_gram; thz_host_pca_components with
+ * that count; thz_pca_scores.  It fills *out and the three resident buffers THZ_BUF_PCA_SCORES (K, npix) /
+ * _COMPONENTS (K, L) / _MEAN (L) (thz_session_buffer, thz_session_download; absent until the first call, and again
+ * after an upload; for the first two the pix0 / npix of thz_session_download count over the flattened array, for the
+ * mean over its L entries).
+ * The covariance is NOT pixel-independent, so a group cannot call thz_session_pca slab by slab.  The three piece calls
+ * are what a group's owner runs on every thz_group_session_member(gs, i): _pca_sums and _pca_gram per member, added on
+ * the host in member order (f64), thz_host_pca_components once, then _pca_project per member with the common mu and
+ * components, which fills that member's three buffers (mu NULL: not centred).  GpuEngine::pca does this for the
+ * members of one process; a collective form for rank processes is not provided. */
+typedef struct thz_pca_cfg {
+    uint32_t first, count, step; /* the columns (bins or samples): first + j * step, j = 0 .. count-1 */
+    int32_t n_components;        /* K, 1 .. min(count, THZ_PCA_MAX_COMPONENTS) */
+    int32_t center;              /* 0: second moments of X itself; otherwise the covariance about the mean */
+    const uint8_t *d_mask;       /* NULL, or one byte per pixel (device): 0 leaves the pixel out of mean and covariance */
+} thz_pca_cfg;
+typedef struct thz_pca_out {
+    double eigenvalues[8];       /* the first n_components, descending; the rest 0 */
+    double total_variance;       /* trace of the covariance */
+    uint64_t count;              /* unmasked pixels */
+} thz_pca_out;
+int thz_session_pca(thz_session *s, int which, const thz_pca_cfg *cfg, thz_pca_out *out);
+int thz_session_pca_sums(thz_session *s, int which, const thz_pca_cfg *cfg, double *sum /* count */, uint64_t *count);
+int thz_session_pca_gram(thz_session *s, int which, const thz_pca_cfg *cfg, const float *mu, double *gram);
+int thz_session_pca_project(thz_session *s, int which, const thz_pca_cfg *cfg, const float *mu,
+                            const float *components);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */
@@ -1033,7 +1118,8 @@ enum {
     THZ_STAGE_PEAK = 12,
     THZ_STAGE_OPTICAL = 13,
     THZ_STAGE_ECHO = 14,
-    THZ_STAGE_COUNT = 15
+    THZ_STAGE_PCA = 15,
+    THZ_STAGE_COUNT = 16
 };
 /* hipEvent bracketing of every stage call on the context's stream.
  *   0  off (default)

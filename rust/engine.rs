@@ -495,6 +495,94 @@ impl GpuEngine {
         }
     }
 
+    /// Principal components of everything this process holds: the covariance is not pixel-independent, so
+    /// `thz_session_pca_sums` and `thz_session_pca_gram` run on each local member, the members' sums and Gram matrices
+    /// are added here in member order (f64), `thz_host_pca_components` runs once, and `thz_session_pca_project` fills
+    /// each member's `THZ_BUF_PCA_SCORES / _COMPONENTS / _MEAN` with the common mean and components.  `which`:
+    /// `THZ_BUF_AMPLITUDES`, `_PHASES`, `_DATA` (whatever the walk has recorded is flushed first) or `_RAW`;
+    /// `cfg.d_mask` is not read: `mask` is empty or one byte per pixel of the whole (gx, gy) grid, 0 leaving the pixel
+    /// out of mean and covariance.
+    /// -> (out; scores (n_components, gx, gy); components (n_components, count); mean (count), zeros when
+    /// `cfg.center == 0`; gx; gy)
+    pub fn pca(&mut self, which: c_int, cfg: &ThzPcaCfg, mask: &[u8]) -> Option<(ThzPcaOut, Vec<f32>, Vec<f32>, Vec<f32>, usize, usize)> {
+        if self.session.is_null() || cfg.count < 1 || cfg.count > THZ_PCA_MAX_LEN as u32 || cfg.n_components < 1
+            || cfg.n_components > THZ_PCA_MAX_COMPONENTS || cfg.n_components as u32 > cfg.count { return None; }
+        if which != THZ_BUF_RAW && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy) = (0usize, 0usize);
+            for i in 0..members {
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut rows[i as usize]);
+                    gy = self.ny;
+                } else {
+                    thz_session_grid(thz_group_session_member(self.session, i), &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                }
+                gx += rows[i as usize];
+            }
+            let (l, k, npix) = (cfg.count as usize, cfg.n_components as usize, gx * gy);
+            if !mask.is_empty() && mask.len() != npix { return None; }
+            // every member's rows of the mask on that member's device, for the length of this call
+            let mut d_mask: Vec<*mut c_void> = vec![ptr::null_mut(); members as usize];
+            let mut cfgs = vec![*cfg; members as usize];
+            let mut ok = true;
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let mine = rows[i as usize] * gy;
+                cfgs[i as usize].d_mask = ptr::null();
+                if ok && !mask.is_empty() && mine > 0 {
+                    let ctx = thz_group_ctx(self.group, i);
+                    ok = thz_malloc(ctx, &mut d_mask[i as usize], mine) == THZ_OK
+                        && thz_memcpy_h2d(ctx, d_mask[i as usize], mask.as_ptr().add(at) as *const c_void, mine) == THZ_OK;
+                    cfgs[i as usize].d_mask = d_mask[i as usize] as *const u8;
+                }
+                at += mine;
+            }
+            // calls 1 and 2 on every member, added in member order
+            let (mut sum, mut gram, mut part) = (vec![0f64; l], vec![0f64; l * l], vec![0f64; l * l]);
+            let mut count = 0u64;
+            for i in 0..members {
+                if !ok || rows[i as usize] == 0 { continue; }
+                let mut n = 0u64;
+                ok = thz_session_pca_sums(thz_group_session_member(self.session, i), which, &cfgs[i as usize], part.as_mut_ptr(), &mut n) == THZ_OK;
+                if ok { for j in 0..l { sum[j] += part[j]; } }
+                count += n;
+            }
+            ok = ok && count >= 2;
+            let mut mean = vec![0f32; l];
+            if ok && cfg.center != 0 { for j in 0..l { mean[j] = (sum[j] / count as f64) as f32; } }
+            let mu: *const f32 = if cfg.center != 0 { mean.as_ptr() } else { ptr::null() };
+            for i in 0..members {
+                if !ok || rows[i as usize] == 0 { continue; }
+                ok = thz_session_pca_gram(thz_group_session_member(self.session, i), which, &cfgs[i as usize], mu, part.as_mut_ptr()) == THZ_OK;
+                if ok { for j in 0..l * l { gram[j] += part[j]; } }
+            }
+            // the components once, then call 4 per member
+            let mut out: ThzPcaOut = std::mem::zeroed();
+            out.count = count;
+            let mut components = vec![0f32; k * l];
+            ok = ok && thz_host_pca_components(gram.as_ptr(), l, count, k as c_int, components.as_mut_ptr(), out.eigenvalues.as_mut_ptr(), &mut out.total_variance) == THZ_OK;
+            let mut scores = vec![0f32; k * npix];
+            at = 0;
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = rows[i as usize] * gy;
+                if !ok || mine == 0 { continue; }
+                ok = thz_session_pca_project(s, which, &cfgs[i as usize], mu, components.as_ptr()) == THZ_OK;
+                for c in 0..k { // a member's scores are component-major over ITS pixels
+                    ok = ok && thz_session_download(s, THZ_BUF_PCA_SCORES, c * mine, mine, scores.as_mut_ptr().add(c * npix + at) as *mut c_void) == THZ_OK;
+                }
+                at += mine;
+            }
+            for i in 0..members {
+                if !d_mask[i as usize].is_null() { thz_free(thz_group_ctx(self.group, i), d_mask[i as usize]); }
+            }
+            if ok { Some((out, scores, components, mean, gx, gy)) } else { None }
+        }
+    }
+
     /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
     /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
     /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and

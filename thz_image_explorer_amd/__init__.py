@@ -15,5 +15,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       OpticalCfg, optical_cfg, OPTICAL_MAX_BANDS, STAGE_OPTICAL, BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA,
                       BUF_OPT_WRAPS, BUF_OPT_SLOPE,
                       EchoCfg, LayerCfg, echo_cfg, layer_cfg, host_echo_trace, ECHO_MAX, LAYER_BETWEEN, LAYER_REFERENCE, STAGE_ECHO,
-                      BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY)
+                      BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY,
+                      PcaCfg, PcaOut, pca_cfg, host_pca_components, PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN, STAGE_PCA,
+                      BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN)
 from . import binding  # noqa: F401

@@ -22,7 +22,7 @@ STATUS = {0: "THZ_OK", -1: "THZ_ERR_INVALID", -2: "THZ_ERR_UNSUPPORTED", -3: "TH
 WIN_ADAPTED_BLACKMAN, WIN_BLACKMAN, WIN_HANNING, WIN_HAMMING, WIN_FLAT_TOP = range(5)
 STAGE_FFT, STAGE_FD_MASK, STAGE_IFFT, STAGE_PIPELINE, STAGE_TD_WINDOW, STAGE_INTENSITY, \
     STAGE_MEAN, STAGE_ROI, STAGE_VOXEL_OPACITY, STAGE_VOXEL_SELECT, STAGE_VOXEL_EMIT, STAGE_PROBE, STAGE_PEAK, \
-    STAGE_OPTICAL, STAGE_ECHO = range(15)
+    STAGE_OPTICAL, STAGE_ECHO, STAGE_PCA = range(16)
 PEAK_ABS, PEAK_MAX, PEAK_MIN = range(3)  # thz_peak_map's mode: largest |x|, maximum, minimum
 
 
@@ -117,9 +117,11 @@ class PlotOut(C.Structure):
 BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BUF_AVG_AMPLITUDES, \
     BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, \
     BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE, \
-    BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY = range(24)
+    BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY, \
+    BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN = range(27)
 OPTICAL_MAX_BANDS = 8
 ECHO_MAX = 4
+PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN = 512, 8, 1024  # THZ_PCA_*: columns, components, products per f32 accumulator
 LAYER_BETWEEN, LAYER_REFERENCE = range(2)  # thz_layer_map's mode: consecutive pulses, rank 0 against a fixed arrival
 
 
@@ -169,6 +171,22 @@ def layer_cfg(mode=LAYER_BETWEEN, scale=(1.0,), ref_index=0, ref_offset=0.0) -> 
     sc = [float(v) for v in np.atleast_1d(scale)][:4]
     cfg = LayerCfg(int(mode), (C.c_float * 4)(*(sc + [sc[-1]] * (4 - len(sc)))), int(ref_index), float(ref_offset))
     return cfg
+
+
+class PcaCfg(C.Structure):
+    """thz_pca_cfg: the columns of the matrix, the number of components, centring and an optional device mask"""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("step", C.c_uint32), ("n_components", C.c_int32),
+                ("center", C.c_int32), ("d_mask", C.c_void_p)]
+
+
+class PcaOut(C.Structure):
+    """thz_pca_out: eigenvalues (descending), trace of the covariance, unmasked pixels"""
+    _fields_ = [("eigenvalues", C.c_double * 8), ("total_variance", C.c_double), ("count", C.c_uint64)]
+
+
+def pca_cfg(first, count, step=1, n_components=3, center=True, mask=None) -> PcaCfg:
+    """mask: device pointer / DevBuf of one uint8 per pixel, or None"""
+    return PcaCfg(int(first), int(count), int(step), int(n_components), int(bool(center)), _dp(mask))
 
 
 class ThzError(RuntimeError):
@@ -293,6 +311,14 @@ SYMBOLS = [
     ("thz_host_echo_trace", C.c_int, [_P, _SZ, C.POINTER(EchoCfg), _P, _P, _P, _P]),
     ("thz_session_echo_map", C.c_int, [_P, C.c_int, C.POINTER(EchoCfg)]),
     ("thz_session_layer_map", C.c_int, [_P, C.POINTER(LayerCfg)]),
+    ("thz_pca_sums", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _P]),
+    ("thz_pca_gram", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _P]),
+    ("thz_host_pca_components", C.c_int, [_P, _SZ, C.c_uint64, C.c_int, _P, _P, _P]),
+    ("thz_pca_scores", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, C.c_int, _P]),
+    ("thz_session_pca", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), C.POINTER(PcaOut)]),
+    ("thz_session_pca_sums", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
+    ("thz_session_pca_gram", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
+    ("thz_session_pca_project", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -482,6 +508,15 @@ def host_echo_trace(x, cfg: EchoCfg):
     return idx, off, val, n.value
 
 
+def host_pca_components(gram, count, k):
+    """thz_host_pca_components -> (rc, components f32 (k, L), eigenvalues f64 (k), total variance)"""
+    g = np.ascontiguousarray(gram, np.float64)
+    n = g.shape[0] if g.ndim == 2 else int(round(np.sqrt(g.size)))
+    comp, ev, tot = np.zeros((max(int(k), 1), n), np.float32), np.zeros(max(int(k), 1), np.float64), C.c_double()
+    rc = load_library().thz_host_pca_components(g.ctypes.data, n, int(count), int(k), comp.ctypes.data, ev.ctypes.data, C.byref(tot))
+    return rc, comp, ev, tot.value
+
+
 def voxel_cfg_default() -> VoxelCfg:
     cfg = VoxelCfg()
     _rc(load_library().thz_voxel_cfg_default(C.byref(cfg)), "voxel_cfg_default")
@@ -665,6 +700,46 @@ class Session:
         rows = k - 1 if cfg.mode == LAYER_BETWEEN else 1
         return tuple(self.download(b, npix=rows * gx * gy).reshape(rows, gx, gy) for b in (BUF_LAYER_THICKNESS, BUF_LAYER_DELAY))
 
+    def _pca_pix(self, which):
+        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        return gx, gy
+
+    def pca(self, which, cfg: "PcaCfg"):
+        """thz_session_pca -> (eigenvalues f64 (K), total variance, count, scores f32 (K, gx, gy), components f32 (K, L),
+        mean f32 (L))"""
+        out = PcaOut()
+        self.eng._check(self.eng.lib.thz_session_pca(self.h, int(which), C.byref(cfg), C.byref(out)))
+        gx, gy = self._pca_pix(which)
+        k, n = int(cfg.n_components), int(cfg.count)
+        return (np.array(out.eigenvalues[:k]), out.total_variance, out.count,
+                self.download(BUF_PCA_SCORES, npix=k * gx * gy).reshape(k, gx, gy),
+                self.download(BUF_PCA_COMPONENTS, npix=k * n).reshape(k, n), self.download(BUF_PCA_MEAN, npix=n))
+
+    def pca_sums(self, which, cfg: "PcaCfg"):
+        """thz_session_pca_sums -> (sum f64 (L), count)"""
+        s, n = np.zeros(int(cfg.count), np.float64), C.c_uint64()
+        self.eng._check(self.eng.lib.thz_session_pca_sums(self.h, int(which), C.byref(cfg), s.ctypes.data, C.byref(n)))
+        return s, n.value
+
+    def pca_gram(self, which, cfg: "PcaCfg", mu=None):
+        """thz_session_pca_gram -> f64 (L, L)"""
+        n = int(cfg.count)
+        g = np.zeros((n, n), np.float64)
+        m = None if mu is None else np.ascontiguousarray(mu, np.float32)
+        self.eng._check(self.eng.lib.thz_session_pca_gram(self.h, int(which), C.byref(cfg), None if m is None else m.ctypes.data,
+                                                          g.ctypes.data))
+        return g
+
+    def pca_project(self, which, cfg: "PcaCfg", mu, components):
+        """thz_session_pca_project -> scores f32 (K, gx, gy); fills the three resident buffers"""
+        m = None if mu is None else np.ascontiguousarray(mu, np.float32)
+        v = np.ascontiguousarray(components, np.float32)
+        self.eng._check(self.eng.lib.thz_session_pca_project(self.h, int(which), C.byref(cfg), None if m is None else m.ctypes.data,
+                                                             v.ctypes.data))
+        gx, gy = self._pca_pix(which)
+        k = int(cfg.n_components)
+        return self.download(BUF_PCA_SCORES, npix=k * gx * gy).reshape(k, gx, gy)
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -688,6 +763,8 @@ class Session:
             out = np.empty(npix, np.int32 if which == BUF_OPT_WRAPS else np.float32)
         elif BUF_ECHO_INDEX <= which <= BUF_LAYER_DELAY:  # npix: entries of the last call's (row, pixel) array, likewise
             out = np.empty(npix, np.int32 if which in (BUF_ECHO_INDEX, BUF_ECHO_COUNT) else np.float32)
+        elif BUF_PCA_SCORES <= which <= BUF_PCA_MEAN:  # npix: entries of the flattened array, likewise
+            out = np.empty(npix, np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -1064,6 +1141,27 @@ class Engine:
         """thz_layer_map: index, offset (n_echoes, npix) -> thickness, delay (n_echoes - 1 or 1, npix), all on the device"""
         self._check(self.lib.thz_layer_map(self.ctx, npix, int(n_echoes), _dp(index), _dp(offset), C.byref(cfg), _dp(thickness),
                                            _dp(delay)))
+
+    def pca_sums(self, npix, n, x, row_stride, col_step=1, mask=None):
+        """thz_pca_sums of the (npix, n) matrix x[p * row_stride + j * col_step] -> (sum f64 (n), count)"""
+        s, cnt = np.zeros(max(int(n), 1), np.float64), C.c_uint64()
+        self._check(self.lib.thz_pca_sums(self.ctx, npix, n, _dp(x), row_stride, col_step, _dp(mask), s.ctypes.data, C.byref(cnt)))
+        return s[:n], cnt.value
+
+    def pca_gram(self, npix, n, x, row_stride, col_step=1, mask=None, mu=None):
+        """thz_pca_gram -> f64 (n, n): the Gram matrix of x - mu over the unmasked pixels"""
+        g = np.zeros((max(int(n), 1),) * 2, np.float64)
+        m = None if mu is None else np.ascontiguousarray(mu, np.float32)
+        self._check(self.lib.thz_pca_gram(self.ctx, npix, n, _dp(x), row_stride, col_step, _dp(mask),
+                                          None if m is None else m.ctypes.data, g.ctypes.data))
+        return g[:n, :n]
+
+    def pca_scores(self, npix, n, x, row_stride, col_step, mu, components, scores):
+        """thz_pca_scores: scores (K, npix) on the device from host mu (or None) and components (K, n)"""
+        m = None if mu is None else np.ascontiguousarray(mu, np.float32)
+        v = np.ascontiguousarray(components, np.float32)
+        self._check(self.lib.thz_pca_scores(self.ctx, npix, n, _dp(x), row_stride, col_step, None if m is None else m.ctypes.data,
+                                            v.ctypes.data, v.shape[0] if v.ndim == 2 else 1, _dp(scores)))
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

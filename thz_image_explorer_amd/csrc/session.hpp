@@ -75,6 +75,11 @@ struct thz_session {
     float *d_layer = nullptr;
     size_t layer_cap = 0;
     size_t layer_pix = 0, layer_rows = 0;
+    // principal components of the last thz_session_pca / _pca_project (pca_api.cpp):
+    // d_pca = [scores: (pca_k, pca_pix), component-major | components: (pca_k, pca_len) | mean: pca_len]
+    float *d_pca = nullptr;
+    size_t pca_cap = 0;                        // floats allocated
+    size_t pca_pix = 0, pca_k = 0, pca_len = 0;  // pixels, components and columns of the last call; 0 pixels: absent
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;

@@ -7,6 +7,7 @@
 // usage: engine_selftest <dir>   (dir/cube.bin, dir/psf.bin as written by the test; outputs dir/<scenario>.bin)
 #include "thz_engine.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -293,6 +294,35 @@ int main(int argc, char **argv)
             CHECK(std::memcmp(t1.data(), t2.data(), t1.size() * sizeof(float)) == 0
                       && std::memcmp(d1.data(), d2.data(), d1.size() * sizeof(float)) == 0,
                   "layer_map over two slabs == over one");
+        }
+        {
+            // principal components of the resident amplitudes, on one slab and on two: the slabs' sums and Gram matrices
+            // are added in f64, so the eigenvalues agree far inside the Gram matrix's own f32 error, and the scores to
+            // the f32 rounding of the components
+            thz_pca_cfg pc{};
+            pc.first = 4; pc.count = 40; pc.step = 2; pc.n_components = 2; pc.center = 1;
+            std::vector<uint8_t> mask((size_t)c.nx * (size_t)c.ny, 1);
+            for (size_t i = 0; i < mask.size(); i += 7) mask[i] = 0;
+            thz_pca_out o1{}, o2{};
+            std::vector<float> s1, s2, v1, v2, m1, m2;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0;
+            CHECK(eng.pca(THZ_BUF_AMPLITUDES, pc, mask, o1, s1, v1, m1, gx1, gy1), "pca on one slab");
+            CHECK(eng2.pca(THZ_BUF_AMPLITUDES, pc, mask, o2, s2, v2, m2, gx2, gy2), "pca on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1, "pca: the whole grid");
+            CHECK(s1.size() == 2 * gx1 * gy1 && s2.size() == s1.size() && v1.size() == 80 && m1.size() == 40, "pca: sizes");
+            CHECK(o1.count == o2.count && o1.count == mask.size() - (mask.size() + 6) / 7, "pca: the unmasked pixels, bit for bit");
+            CHECK(o1.eigenvalues[0] >= o1.eigenvalues[1] && o1.eigenvalues[1] > 0.0 && o1.total_variance >= o1.eigenvalues[0] + o1.eigenvalues[1] * 0.999,
+                  "pca: eigenvalues in descending order inside the total variance");
+            double worst_ev = 0.0, worst_s = 0.0, big_s = 0.0;
+            for (int k = 0; k < 2; ++k) worst_ev = std::max(worst_ev, std::fabs(o1.eigenvalues[k] - o2.eigenvalues[k]) / o1.eigenvalues[0]);
+            for (size_t i = 0; i < gx1 * gy1; ++i) {  // the leading component's score image
+                worst_s = std::max(worst_s, (double)std::fabs(s1[i] - s2[i]));
+                big_s = std::max(big_s, (double)std::fabs(s1[i]));
+            }
+            std::printf("pca: eigenvalues %.6g %.6g of %.6g; two slabs against one: eigenvalues %.3g (relative), scores %.3g of %.3g\n",
+                        o1.eigenvalues[0], o1.eigenvalues[1], o1.total_variance, worst_ev, worst_s, big_s);
+            CHECK(worst_ev < 1e-5, "pca over two slabs == over one (eigenvalues)");
+            CHECK(worst_s < 1e-3 * big_s, "pca over two slabs == over one (leading score image)");
         }
         small_bank(q.filter_by("Deconvolution"));
         q.filters_active[q.filter_chain[q.index_of("Deconvolution")]] = true;

@@ -468,6 +468,89 @@ bool GpuEngine::layer_map(const thz_layer_cfg &cfg, std::vector<float> &thicknes
     }
     return true;
 }
+bool GpuEngine::pca(int which, const thz_pca_cfg &cfg, const std::vector<uint8_t> &mask, thz_pca_out &out, std::vector<float> &scores,
+                    std::vector<float> &components, std::vector<float> &mean, size_t &gx, size_t &gy)
+{
+    gx = gy = 0;
+    out = thz_pca_out{};
+    if (!session_ || cfg.count < 1 || cfg.count > THZ_PCA_MAX_LEN || cfg.n_components < 1 || cfg.n_components > THZ_PCA_MAX_COMPONENTS
+        || (uint32_t)cfg.n_components > cfg.count)
+        return false;
+    if (which != THZ_BUF_RAW && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &rows[(size_t)i]);
+            gy = ny;
+        } else {
+            thz_session_grid(thz_group_session_member(session_, i), &rows[(size_t)i], &gy, nullptr, nullptr);
+        }
+        gx += rows[(size_t)i];
+    }
+    const size_t L = cfg.count, K = (size_t)cfg.n_components, npix = gx * gy;
+    if (!mask.empty() && mask.size() != npix) return false;
+    // every member's rows of the mask on that member's device, for the length of this call
+    std::vector<void *> d_mask((size_t)members, nullptr);
+    auto release = [&]() {
+        for (int i = 0; i < members; ++i)
+            if (d_mask[(size_t)i]) thz_free(thz_group_ctx(group_, i), d_mask[(size_t)i]);
+    };
+    std::vector<thz_pca_cfg> cfgs((size_t)members, cfg);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        const size_t mine = rows[(size_t)i] * gy;
+        cfgs[(size_t)i].d_mask = nullptr;
+        if (!mask.empty() && mine) {
+            thz_ctx *ctx = thz_group_ctx(group_, i);
+            if (thz_malloc(ctx, &d_mask[(size_t)i], mine) != THZ_OK || thz_memcpy_h2d(ctx, d_mask[(size_t)i], mask.data() + at, mine) != THZ_OK) {
+                release();
+                return false;
+            }
+            cfgs[(size_t)i].d_mask = static_cast<const uint8_t *>(d_mask[(size_t)i]);
+        }
+        at += mine;
+    }
+    // calls 1 and 2 on every member, added in member order
+    std::vector<double> sum(L, 0.0), gram(L * L, 0.0), part(L * L);
+    uint64_t count = 0;
+    bool ok = true;
+    for (int i = 0; ok && i < members; ++i) {
+        if (!rows[(size_t)i]) continue;
+        uint64_t n = 0;
+        ok = thz_session_pca_sums(thz_group_session_member(session_, i), which, &cfgs[(size_t)i], part.data(), &n) == THZ_OK;
+        for (size_t j = 0; ok && j < L; ++j) sum[j] += part[j];
+        count += n;
+    }
+    out.count = count;
+    ok = ok && count >= 2;
+    mean.assign(L, 0.0f);
+    if (ok && cfg.center)
+        for (size_t j = 0; j < L; ++j) mean[j] = (float)(sum[j] / (double)count);
+    const float *mu = cfg.center ? mean.data() : nullptr;
+    for (int i = 0; ok && i < members; ++i) {
+        if (!rows[(size_t)i]) continue;
+        ok = thz_session_pca_gram(thz_group_session_member(session_, i), which, &cfgs[(size_t)i], mu, part.data()) == THZ_OK;
+        for (size_t j = 0; ok && j < L * L; ++j) gram[j] += part[j];
+    }
+    // the components once, then call 4 per member
+    components.assign(K * L, 0.0f);
+    ok = ok && thz_host_pca_components(gram.data(), L, count, (int)K, components.data(), out.eigenvalues, &out.total_variance) == THZ_OK;
+    scores.assign(K * npix, 0.0f);
+    at = 0;
+    for (int i = 0; ok && i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = rows[(size_t)i] * gy;
+        if (!mine) continue;
+        ok = thz_session_pca_project(s, which, &cfgs[(size_t)i], mu, components.data()) == THZ_OK;
+        for (size_t c = 0; ok && c < K; ++c)  // a member's scores are component-major over ITS pixels
+            ok = thz_session_download(s, THZ_BUF_PCA_SCORES, c * mine, mine, scores.data() + c * npix + at) == THZ_OK;
+        at += mine;
+    }
+    release();
+    return ok;
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;

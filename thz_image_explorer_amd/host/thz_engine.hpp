@@ -91,6 +91,15 @@ public:
     // THZ_BUF_LAYER_THICKNESS stays resident: a row of it is a valid d_thickness of thz_session_optical_maps
     bool layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,
                    size_t &gx, size_t &gy);
+    // Principal components of everything this process holds: the covariance is not pixel-independent, so
+    // thz_session_pca_sums and thz_session_pca_gram run on each local member, the members' sums and Gram matrices are
+    // added here in member order (f64), thz_host_pca_components runs once, and thz_session_pca_project fills each
+    // member's THZ_BUF_PCA_SCORES / _COMPONENTS / _MEAN with the common mean and components.  which: THZ_BUF_AMPLITUDES,
+    // _PHASES, _DATA (whatever the walk has recorded is flushed first) or _RAW; cfg.d_mask is not read: mask is empty or
+    // one byte per pixel of the whole (gx, gy) grid, 0 leaving the pixel out of mean and covariance.
+    // scores: (n_components, gx, gy); components: (n_components, count); mean: (count), zeros when cfg.center == 0
+    bool pca(int which, const thz_pca_cfg &cfg, const std::vector<uint8_t> &mask, thz_pca_out &out, std::vector<float> &scores,
+             std::vector<float> &components, std::vector<float> &mean, size_t &gx, size_t &gy);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
