@@ -603,6 +603,46 @@ int thz_host_pca_components(const double *gram, size_t L, uint64_t count, int K,
 int thz_pca_scores(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
                    const float *mu, const float *components, int K, float *d_scores /* (K, npix) */);
 
+/* ------------------------------------------------------------------ */
+/* Segmenting a scan into materials: k-means (K20)     */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  "Which pixels belong together?" is k-means of the pixels' rows: one label image and one
+ * mean row (the mean spectrum of a material) per cluster.  One device call is one step of Lloyd's algorithm; the
+ * centroid update is plain C++, so the slabs of a group are added on the host between the two.
+ *
+ * thz_cluster_step sees the matrix of the PCA calls above — X[p, j] = d_x[p * row_stride + j * col_step], 1 <= L <=
+ * THZ_PCA_MAX_LEN, 4-byte alignment only, the optional d_mask of npix uint8 — and K x L host floats `centroids`,
+ * 1 <= K <= THZ_CLUSTER_MAX, which go up once per call.
+ *   assignment   for EVERY pixel, masked ones included, one wave per pixel with the centroids in LDS:
+ *                dist2[c] = sum_j (X[p, j] - m[c, j])^2 in f32, d = x - m ONE f32 subtraction, lane l adding
+ *                fmaf(d, d, acc) over j = l, l + 64, ... in ascending order, then the lanes as the fixed tree of
+ *                thz_pca_scores — the order depends on L alone, and |dist2 - exact| <= (ceil(L / 64) + 9) 2^-24 exact.
+ *                d_label[p] = the lowest c with the smallest dist2[c]; a NaN never wins; when all K are NaN the label
+ *                is -1 and d_dist2[p] NaN, otherwise d_dist2[p] is the winner's.  *changed counts the pixels whose
+ *                label differs from the one d_label held BEFORE the call (it is read, then overwritten; an integer
+ *                count): a caller starts a run with d_label filled with -1.
+ *   sums         over the unmasked pixels with label >= 0, all in f64 over fixed slabs of pixels whose partials a
+ *                second kernel adds in slab order (no floating-point atomics: the same bits on every run):
+ *                sums[c * L + j] = sum of X[p, j] over the pixels of cluster c (sums may be NULL: not returned),
+ *                counts[c] their number, *inertia = sum of d_dist2[p], *farthest = the index of the pixel with the
+ *                largest finite d_dist2, the lowest index winning a tie, npix when there is none.
+ * THZ_ERR_INVALID, before any launch or allocation, for anything outside these limits or a required pointer that is
+ * NULL (all but d_mask and sums); npix == 0 is a no-op that returns zeros.  NaN and Inf get no special case beyond the
+ * label rule.  Time of the launches under THZ_STAGE_PCA.
+ *
+ * thz_host_cluster_update is plain C++, no GPU and no context: centroids[c, j] = (float)(sums[c, j] / counts[c]) in
+ * f64; a cluster with counts[c] == 0 keeps previous[c, :] bit for bit (previous and centroids may be the same array).
+ * THZ_ERR_INVALID for K outside 1 .. THZ_CLUSTER_MAX, L outside 1 .. THZ_PCA_MAX_LEN, a NULL pointer, or a non-finite
+ * sum. */
+#define THZ_CLUSTER_MAX 16
+int thz_cluster_step(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
+                     const uint8_t *d_mask, const float *centroids /* K x L host */, int K,
+                     int32_t *d_label, float *d_dist2 /* device, npix; d_label is read AND written */,
+                     double *sums /* K x L host or NULL */, uint64_t *counts /* K */, double *inertia,
+                     uint64_t *changed, uint64_t *farthest);
+int thz_host_cluster_update(const double *sums, const uint64_t *counts, int K, size_t L,
+                            const float *previous /* K x L */, float *centroids /* K x L */);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -704,7 +744,10 @@ enum {
     THZ_BUF_LAYER_DELAY = 23, /* likewise */
     THZ_BUF_PCA_SCORES = 24,  /* (K, npix) f32 of the last thz_session_pca / _pca_project, component-major */
     THZ_BUF_PCA_COMPONENTS = 25, /* (K, L) f32 */
-    THZ_BUF_PCA_MEAN = 26     /* (L) f32; zeros when the call did not centre */
+    THZ_BUF_PCA_MEAN = 26,    /* (L) f32; zeros when the call did not centre */
+    THZ_BUF_CLUSTER_LABELS = 27, /* (npix) int32 of the last thz_session_cluster / _cluster_step; -1: every distance NaN */
+    THZ_BUF_CLUSTER_DIST = 28,   /* (npix) f32: squared distance to the pixel's centroid */
+    THZ_BUF_CLUSTER_CENTROIDS = 29 /* (K, L) f32: the centroids the labels belong to, one mean row per cluster */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -869,6 +912,56 @@ int thz_session_pca_sums(thz_session *s, int which, const thz_pca_cfg *cfg, doub
 int thz_session_pca_gram(thz_session *s, int which, const thz_pca_cfg *cfg, const float *mu, double *gram);
 int thz_session_pca_project(thz_session *s, int which, const thz_pca_cfg *cfg, const float *mu,
                             const float *components);
+
+/* k-means of the pixels of a resident cube.  `which` and the columns first / count / step name the matrix exactly as
+ * for thz_session_pca (same grids, same THZ_ERR_NOT_READY / THZ_ERR_INVALID cases), read in place through the session's
+ * own pointers; in addition THZ_BUF_PCA_SCORES names the score images of the last thz_session_pca / _pca_project: the
+ * columns are then the components (first + j * step < K of that call), the pixels those of the score images, and the
+ * call is THZ_ERR_NOT_READY before a PCA call.  n_clusters in 1 .. THZ_CLUSTER_MAX, init 0 or 1, max_iter in
+ * 1 .. 1000, centroids not NULL when init == 0: anything else is THZ_ERR_INVALID.
+ *
+ * thz_session_cluster:
+ *   seeds    init 0: cfg->centroids.  init 1, farthest-first: mu = (float)(sum / count) from thz_pca_sums
+ *            (THZ_ERR_INVALID when no pixel is unmasked); c_0 = the row of the pixel farthest from mu (a step with
+ *            K = 1; THZ_ERR_INVALID when no distance is finite); c_k = the row of the pixel farthest from its nearest
+ *            of c_0 .. c_k-1 (a step with K = k); with no finite farthest pixel the remaining seeds repeat the last
+ *            one — ties go to the lowest label, so the repeats stay empty.
+ *   loop     the labels start at -1; a step, then thz_host_cluster_update, until a step reports changed == 0
+ *            (converged = 1) or max_iter steps have run.  No update follows the last step: the centroids kept are the
+ *            ones that step used, so labels, distances and centroids belong together.
+ *   *out     inertia, counts and their sum of the last step, the steps run and whether the last one changed nothing.
+ * It fills the resident buffers THZ_BUF_CLUSTER_LABELS (npix int32) / _DIST (npix f32) / _CENTROIDS (K, L f32)
+ * (thz_session_buffer, thz_session_download, whose pix0 / npix count entries of the flattened array; absent until
+ * the first call, and again after an upload).  The centroid rows are the mean spectra per material.
+ *
+ * Clustering is NOT pixel-independent, so a group cannot call thz_session_cluster slab by slab.  The two piece calls
+ * are what a group's owner runs on every thz_group_session_member(gs, i):
+ *   thz_session_cluster_step  one thz_cluster_step on the member's matrix and its resident labels and distances, with
+ *            K = cfg->n_clusters rows in `centroids`, which become THZ_BUF_CLUSTER_CENTROIDS.  cfg->init != 0 fills
+ *            the labels with -1 first (every seeding step and the first step of a loop); the buffers are also
+ *            started afresh when the number of pixels has changed.  cfg->max_iter and cfg->centroids are not read.
+ *            The owner adds sums, counts, inertia and changed in member order and takes the farthest pixel as the
+ *            largest THZ_BUF_CLUSTER_DIST entry among the members' candidates, the lowest global index winning a tie.
+ *   thz_session_cluster_row   the `count` values of row `pixel` of the member's matrix, to the host.
+ * GpuEngine::cluster does this for the members of one process; a collective form for rank processes is not provided. */
+typedef struct thz_cluster_cfg {
+    uint32_t first, count, step;  /* the columns (bins, samples or components), exactly as thz_pca_cfg */
+    int32_t n_clusters;           /* K, 1 .. THZ_CLUSTER_MAX */
+    int32_t init;                 /* 0: cfg->centroids; 1: farthest-first */
+    int32_t max_iter;             /* 1 .. 1000 */
+    const uint8_t *d_mask;        /* NULL, or one byte per pixel (device): 0 leaves the pixel out of sums, seeds and inertia */
+    const float *centroids;       /* init 0: K x count host floats */
+} thz_cluster_cfg;
+typedef struct thz_cluster_out {
+    double inertia;               /* sum of the squared distances of the unmasked, labelled pixels */
+    uint64_t count;               /* those pixels */
+    uint64_t counts[16];          /* per cluster; the entries from n_clusters on are 0 */
+    int32_t iterations, converged;
+} thz_cluster_out;
+int thz_session_cluster(thz_session *s, int which, const thz_cluster_cfg *cfg, thz_cluster_out *out);
+int thz_session_cluster_step(thz_session *s, int which, const thz_cluster_cfg *cfg, const float *centroids,
+                             double *sums, uint64_t *counts, double *inertia, uint64_t *changed, uint64_t *farthest);
+int thz_session_cluster_row(thz_session *s, int which, const thz_cluster_cfg *cfg, uint64_t pixel, float *row /* count */);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */

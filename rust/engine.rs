@@ -583,6 +583,142 @@ impl GpuEngine {
         }
     }
 
+    /// k-means of everything this process holds: clustering is not pixel-independent, so `thz_session_cluster_step` runs on
+    /// each local member and the members' sums, counts, inertia and changed are added here in member order (f64); the
+    /// farthest pixel is the largest `THZ_BUF_CLUSTER_DIST` entry among the members' candidates, the lowest global index
+    /// winning a tie, and `thz_session_cluster_row` fetches its row; `thz_host_cluster_update` runs once per step, and every
+    /// member iterates with the common centroids.  The mean the seeding starts from is the sum of a K = 1 step about the
+    /// zero vector (rows with a NaN are left out of it).  `which`: what `thz_session_cluster` takes;
+    /// `THZ_BUF_PCA_SCORES` means the score images of the last `pca()` of the recompute's grid and takes no mask.
+    /// `cfg.d_mask` is not read: `mask` is empty or one byte per pixel of the whole (gx, gy) grid.  Every member's
+    /// `THZ_BUF_CLUSTER_LABELS / _DIST / _CENTROIDS` stay resident.
+    /// -> (out; labels (gx, gy); dist2 (gx, gy); centroids (n_clusters, count); gx; gy)
+    pub fn cluster(&mut self, which: c_int, cfg: &ThzClusterCfg, mask: &[u8]) -> Option<(ThzClusterOut, Vec<i32>, Vec<f32>, Vec<f32>, usize, usize)> {
+        if self.session.is_null() || cfg.count < 1 || cfg.count > THZ_PCA_MAX_LEN as u32 || cfg.n_clusters < 1
+            || cfg.n_clusters > THZ_CLUSTER_MAX || (cfg.init != 0 && cfg.init != 1) || cfg.max_iter < 1 || cfg.max_iter > 1000
+            || (cfg.init == 0 && cfg.centroids.is_null()) || (which == THZ_BUF_PCA_SCORES && !mask.is_empty()) { return None; }
+        if which != THZ_BUF_RAW && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy) = (0usize, 0usize);
+            for i in 0..members {
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut rows[i as usize]);
+                    gy = self.ny;
+                } else {
+                    thz_session_grid(thz_group_session_member(self.session, i), &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                }
+                gx += rows[i as usize];
+            }
+            let (l, k_all, npix) = (cfg.count as usize, cfg.n_clusters as usize, gx * gy);
+            if npix == 0 || (!mask.is_empty() && mask.len() != npix) { return None; }
+            // every member's rows of the mask on that member's device, for the length of this call
+            let mut d_mask: Vec<*mut c_void> = vec![ptr::null_mut(); members as usize];
+            let mut cfgs = vec![*cfg; members as usize];
+            let pix: Vec<usize> = rows.iter().map(|r| r * gy).collect();
+            let mut ok = true;
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members as usize {
+                cfgs[i].d_mask = ptr::null();
+                if ok && !mask.is_empty() && pix[i] > 0 {
+                    let ctx = thz_group_ctx(self.group, i as c_int);
+                    ok = thz_malloc(ctx, &mut d_mask[i], pix[i]) == THZ_OK
+                        && thz_memcpy_h2d(ctx, d_mask[i], mask.as_ptr().add(at) as *const c_void, pix[i]) == THZ_OK;
+                    cfgs[i].d_mask = d_mask[i] as *const u8;
+                }
+                at += pix[i];
+            }
+            // one step on every member with k rows of `cent`, added in member order
+            // -> (sums, counts, inertia, changed, the farthest pixel's global index or npix)
+            let session = self.session;
+            let step = |cent: &[f32], k: usize, reset: bool, want_sums: bool| -> Option<(Vec<f64>, [u64; 16], f64, u64, usize)> {
+                let (mut sums, mut part) = (vec![0f64; k * l], vec![0f64; k * l]);
+                let (mut counts, mut inertia, mut changed, mut far, mut best, mut before) = ([0u64; 16], 0f64, 0u64, npix, -1f32, 0usize);
+                for i in 0..members as usize {
+                    if pix[i] == 0 { continue; }
+                    let s = thz_group_session_member(session, i as c_int);
+                    let mut c = cfgs[i];
+                    c.n_clusters = k as i32;
+                    c.init = reset as i32;
+                    let (mut n, mut e, mut ch, mut f) = ([0u64; 16], 0f64, 0u64, 0u64);
+                    let p = if want_sums { part.as_mut_ptr() } else { ptr::null_mut() };
+                    if thz_session_cluster_step(s, which, &c, cent.as_ptr(), p, n.as_mut_ptr(), &mut e, &mut ch, &mut f) != THZ_OK { return None; }
+                    if want_sums { for j in 0..k * l { sums[j] += part[j]; } }
+                    for j in 0..k { counts[j] += n[j]; }
+                    inertia += e;
+                    changed += ch;
+                    if (f as usize) < pix[i] {
+                        let mut v = 0f32;
+                        if thz_session_download(s, THZ_BUF_CLUSTER_DIST, f as usize, 1, &mut v as *mut f32 as *mut c_void) != THZ_OK { return None; }
+                        if v > best { best = v; far = before + f as usize; } // members ascend in the global index: the first stays
+                    }
+                    before += pix[i];
+                }
+                Some((sums, counts, inertia, changed, far))
+            };
+            let row = |mut p: usize, dst: &mut [f32]| -> bool {
+                for i in 0..members as usize {
+                    if p < pix[i] { return thz_session_cluster_row(thz_group_session_member(session, i as c_int), which, &cfgs[i], p as u64, dst.as_mut_ptr()) == THZ_OK; }
+                    p -= pix[i];
+                }
+                false
+            };
+            let mut centroids = vec![0f32; k_all * l];
+            if ok && cfg.init == 0 {
+                ptr::copy_nonoverlapping(cfg.centroids, centroids.as_mut_ptr(), k_all * l);
+            } else if ok {
+                // farthest-first: the mean from the sums about the zero vector, then the farthest pixel each time
+                let mut mean = vec![0f32; l];
+                match step(&mean, 1, true, true) {
+                    Some((sums, counts, _, _, _)) if counts[0] > 0 => { for j in 0..l { mean[j] = (sums[j] / counts[0] as f64) as f32; } }
+                    _ => ok = false,
+                }
+                for k in 0..k_all {
+                    if !ok { break; }
+                    let got = if k == 0 { step(&mean, 1, true, false) } else { step(&centroids[..k * l], k, true, false) };
+                    match got {
+                        Some((_, _, _, _, far)) if far < npix => ok = row(far, &mut centroids[k * l..(k + 1) * l]),
+                        Some(_) if k > 0 => centroids.copy_within((k - 1) * l..k * l, k * l),
+                        _ => ok = false,
+                    }
+                }
+            }
+            let mut out: ThzClusterOut = std::mem::zeroed();
+            let mut next = vec![0f32; k_all * l];
+            for it in 1..=cfg.max_iter {
+                if !ok { break; }
+                match step(&centroids, k_all, it == 1, true) {
+                    Some((sums, counts, inertia, changed, _)) => {
+                        out.iterations = it;
+                        out.converged = (changed == 0) as i32;
+                        out.inertia = inertia;
+                        out.count = 0;
+                        for c in 0..k_all { out.counts[c] = counts[c]; out.count += counts[c]; }
+                        if changed == 0 || it == cfg.max_iter { break; }
+                        ok = thz_host_cluster_update(sums.as_ptr(), counts.as_ptr(), k_all as c_int, l, centroids.as_ptr(), next.as_mut_ptr()) == THZ_OK;
+                        std::mem::swap(&mut centroids, &mut next);
+                    }
+                    None => ok = false,
+                }
+            }
+            let (mut labels, mut dist2) = (vec![-1i32; npix], vec![0f32; npix]);
+            at = 0;
+            for i in 0..members as usize {
+                if !ok || pix[i] == 0 { continue; }
+                let s = thz_group_session_member(self.session, i as c_int);
+                ok = thz_session_download(s, THZ_BUF_CLUSTER_LABELS, 0, pix[i], labels.as_mut_ptr().add(at) as *mut c_void) == THZ_OK
+                    && thz_session_download(s, THZ_BUF_CLUSTER_DIST, 0, pix[i], dist2.as_mut_ptr().add(at) as *mut c_void) == THZ_OK;
+                at += pix[i];
+            }
+            for i in 0..members as usize {
+                if !d_mask[i].is_null() { thz_free(thz_group_ctx(self.group, i as c_int), d_mask[i]); }
+            }
+            if ok { Some((out, labels, dist2, centroids, gx, gy)) } else { None }
+        }
+    }
+
     /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
     /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
     /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and

@@ -17,5 +17,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       EchoCfg, LayerCfg, echo_cfg, layer_cfg, host_echo_trace, ECHO_MAX, LAYER_BETWEEN, LAYER_REFERENCE, STAGE_ECHO,
                       BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY,
                       PcaCfg, PcaOut, pca_cfg, host_pca_components, PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN, STAGE_PCA,
-                      BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN)
+                      BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN,
+                      ClusterCfg, ClusterOut, cluster_cfg, host_cluster_update, CLUSTER_MAX, CLUSTER_INIT_GIVEN, CLUSTER_INIT_FARTHEST,
+                      BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS)
 from . import binding  # noqa: F401

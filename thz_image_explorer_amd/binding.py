@@ -118,10 +118,13 @@ BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BU
     BUF_AVG_PHASES, BUF_OPACITY, BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE, \
     BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE, \
     BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY, \
-    BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN = range(27)
+    BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN, \
+    BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS = range(30)
 OPTICAL_MAX_BANDS = 8
 ECHO_MAX = 4
 PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN = 512, 8, 1024  # THZ_PCA_*: columns, components, products per f32 accumulator
+CLUSTER_MAX = 16  # THZ_CLUSTER_MAX: clusters of one k-means call
+CLUSTER_INIT_GIVEN, CLUSTER_INIT_FARTHEST = range(2)  # thz_cluster_cfg's init
 LAYER_BETWEEN, LAYER_REFERENCE = range(2)  # thz_layer_map's mode: consecutive pulses, rank 0 against a fixed arrival
 
 
@@ -187,6 +190,29 @@ class PcaOut(C.Structure):
 def pca_cfg(first, count, step=1, n_components=3, center=True, mask=None) -> PcaCfg:
     """mask: device pointer / DevBuf of one uint8 per pixel, or None"""
     return PcaCfg(int(first), int(count), int(step), int(n_components), int(bool(center)), _dp(mask))
+
+
+class ClusterCfg(C.Structure):
+    """thz_cluster_cfg: the columns of the matrix, the number of clusters, the seeding, the step limit, an optional device
+    mask and (init 0) the host centroids"""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("step", C.c_uint32), ("n_clusters", C.c_int32),
+                ("init", C.c_int32), ("max_iter", C.c_int32), ("d_mask", C.c_void_p), ("centroids", C.c_void_p)]
+
+
+class ClusterOut(C.Structure):
+    """thz_cluster_out: inertia, labelled unmasked pixels, pixels per cluster, steps run, whether the last changed nothing"""
+    _fields_ = [("inertia", C.c_double), ("count", C.c_uint64), ("counts", C.c_uint64 * 16), ("iterations", C.c_int32),
+                ("converged", C.c_int32)]
+
+
+def cluster_cfg(first, count, step=1, n_clusters=3, init=CLUSTER_INIT_FARTHEST, max_iter=100, mask=None, centroids=None) -> ClusterCfg:
+    """mask: device pointer / DevBuf of one uint8 per pixel, or None; centroids: (n_clusters, count) host floats for
+    init 0 — the array is kept alive by the returned struct"""
+    cfg = ClusterCfg(int(first), int(count), int(step), int(n_clusters), int(init), int(max_iter), _dp(mask), None)
+    if centroids is not None:
+        cfg._centroids = np.ascontiguousarray(centroids, np.float32)
+        cfg.centroids = cfg._centroids.ctypes.data
+    return cfg
 
 
 class ThzError(RuntimeError):
@@ -319,6 +345,11 @@ SYMBOLS = [
     ("thz_session_pca_sums", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
     ("thz_session_pca_gram", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
     ("thz_session_pca_project", C.c_int, [_P, C.c_int, C.POINTER(PcaCfg), _P, _P]),
+    ("thz_cluster_step", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    ("thz_host_cluster_update", C.c_int, [_P, _P, C.c_int, _SZ, _P, _P]),
+    ("thz_session_cluster", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), C.POINTER(ClusterOut)]),
+    ("thz_session_cluster_step", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), _P, _P, _P, _P, _P, _P]),
+    ("thz_session_cluster_row", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), C.c_uint64, _P]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -515,6 +546,17 @@ def host_pca_components(gram, count, k):
     comp, ev, tot = np.zeros((max(int(k), 1), n), np.float32), np.zeros(max(int(k), 1), np.float64), C.c_double()
     rc = load_library().thz_host_pca_components(g.ctypes.data, n, int(count), int(k), comp.ctypes.data, ev.ctypes.data, C.byref(tot))
     return rc, comp, ev, tot.value
+
+
+def host_cluster_update(sums, counts, previous):
+    """thz_host_cluster_update -> (rc, centroids f32 (K, L)); sums f64 (K, L), counts (K), previous f32 (K, L)"""
+    t = np.ascontiguousarray(sums, np.float64)
+    n = np.ascontiguousarray(counts, np.uint64)
+    prev = np.ascontiguousarray(previous, np.float32)
+    k, width = (t.shape if t.ndim == 2 else (1, t.size))
+    out = np.zeros((max(k, 1), max(width, 1)), np.float32)
+    rc = load_library().thz_host_cluster_update(t.ctypes.data, n.ctypes.data, int(k), int(width), prev.ctypes.data, out.ctypes.data)
+    return rc, out[:k, :width]
 
 
 def voxel_cfg_default() -> VoxelCfg:
@@ -740,6 +782,43 @@ class Session:
         k = int(cfg.n_components)
         return self.download(BUF_PCA_SCORES, npix=k * gx * gy).reshape(k, gx, gy)
 
+    def cluster(self, which, cfg: "ClusterCfg"):
+        """thz_session_cluster -> (ClusterOut, labels int32 (npix), dist2 f32 (npix), centroids f32 (K, L)); npix: the
+        pixels of the matrix, flattened"""
+        out = ClusterOut()
+        self.eng._check(self.eng.lib.thz_session_cluster(self.h, int(which), C.byref(cfg), C.byref(out)))
+        return (out,) + self.cluster_buffers(which, cfg)
+
+    def cluster_buffers(self, which, cfg: "ClusterCfg", npix=None):
+        """the three resident buffers of the last call -> (labels, dist2, centroids)"""
+        if npix is None:
+            if which == BUF_PCA_SCORES:
+                raise ValueError("npix is needed for BUF_PCA_SCORES")
+            gx, gy = self._pca_pix(which)
+            npix = gx * gy
+        k, n = int(cfg.n_clusters), int(cfg.count)
+        return (self.download(BUF_CLUSTER_LABELS, npix=npix), self.download(BUF_CLUSTER_DIST, npix=npix),
+                self.download(BUF_CLUSTER_CENTROIDS, npix=k * n).reshape(k, n))
+
+    def cluster_step(self, which, cfg: "ClusterCfg", centroids, want_sums=True):
+        """thz_session_cluster_step with cfg.n_clusters rows of centroids -> (sums f64 (K, L) or None, counts (K),
+        inertia, changed, farthest)"""
+        m = np.ascontiguousarray(centroids, np.float32)
+        k, n = int(cfg.n_clusters), int(cfg.count)
+        assert m.size == k * n
+        sums = np.zeros((k, n), np.float64) if want_sums else None
+        counts, inertia, changed, far = np.zeros(k, np.uint64), C.c_double(), C.c_uint64(), C.c_uint64()
+        self.eng._check(self.eng.lib.thz_session_cluster_step(self.h, int(which), C.byref(cfg), m.ctypes.data,
+                                                              None if sums is None else sums.ctypes.data, counts.ctypes.data,
+                                                              C.byref(inertia), C.byref(changed), C.byref(far)))
+        return sums, counts, inertia.value, changed.value, far.value
+
+    def cluster_row(self, which, cfg: "ClusterCfg", pixel):
+        """thz_session_cluster_row -> f32 (count)"""
+        row = np.zeros(int(cfg.count), np.float32)
+        self.eng._check(self.eng.lib.thz_session_cluster_row(self.h, int(which), C.byref(cfg), int(pixel), row.ctypes.data))
+        return row
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -765,6 +844,8 @@ class Session:
             out = np.empty(npix, np.int32 if which in (BUF_ECHO_INDEX, BUF_ECHO_COUNT) else np.float32)
         elif BUF_PCA_SCORES <= which <= BUF_PCA_MEAN:  # npix: entries of the flattened array, likewise
             out = np.empty(npix, np.float32)
+        elif BUF_CLUSTER_LABELS <= which <= BUF_CLUSTER_CENTROIDS:  # npix: entries of the flattened array, likewise
+            out = np.empty(npix, np.int32 if which == BUF_CLUSTER_LABELS else np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -1162,6 +1243,18 @@ class Engine:
         v = np.ascontiguousarray(components, np.float32)
         self._check(self.lib.thz_pca_scores(self.ctx, npix, n, _dp(x), row_stride, col_step, None if m is None else m.ctypes.data,
                                             v.ctypes.data, v.shape[0] if v.ndim == 2 else 1, _dp(scores)))
+
+    def cluster_step(self, npix, n, x, row_stride, col_step, mask, centroids, label, dist2, want_sums=True):
+        """thz_cluster_step on device label (int32, read and written) and dist2 (f32) -> (sums f64 (K, n) or None,
+        counts (K), inertia, changed, farthest)"""
+        m = np.ascontiguousarray(centroids, np.float32)
+        k = m.shape[0] if m.ndim == 2 else 1
+        sums = np.zeros((max(k, 1), max(int(n), 1)), np.float64) if want_sums else None
+        counts, inertia, changed, far = np.zeros(max(k, 1), np.uint64), C.c_double(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.thz_cluster_step(self.ctx, npix, n, _dp(x), row_stride, col_step, _dp(mask), m.ctypes.data, k, _dp(label),
+                                              _dp(dist2), None if sums is None else sums.ctypes.data, counts.ctypes.data,
+                                              C.byref(inertia), C.byref(changed), C.byref(far)))
+        return (None if sums is None else sums[:k, :n]), counts[:k], inertia.value, changed.value, far.value
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

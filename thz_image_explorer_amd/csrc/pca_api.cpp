@@ -7,8 +7,6 @@
 
 using namespace thz;
 
-namespace {
-
 // the argument rules every device call shares, checked before anything is launched or allocated
 const char *pca_view_error(size_t L, const float *d_x, size_t row_stride, size_t col_step)
 {
@@ -19,28 +17,29 @@ const char *pca_view_error(size_t L, const float *d_x, size_t row_stride, size_t
     return nullptr;
 }
 
+namespace {
+
 PcaView view_of(size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step, const uint8_t *d_mask)
 {
     return PcaView{d_x, npix, (int)L, row_stride, col_step, d_mask};
 }
 
-// what `which` and cfg name in a session: the matrix, or the error
-struct SessionMatrix {
-    const float *d = nullptr;
-    size_t npix = 0, L = 0, row_stride = 0, col_step = 0;
-};
-int session_matrix(thz_session *s, int which, const thz_pca_cfg *cfg, SessionMatrix *m)
+}  // namespace
+
+// what `which` and the columns of cfg name in a session: the matrix, or the error (`what` starts its message)
+int session_matrix(thz_session *s, int which, const thz_pca_cfg *cfg, const char *what, SessionMatrix *m)
 {
+    const std::string of = std::string(what) + ": ";
     thz_ctx *ctx = s->ctx;
     if (which != THZ_BUF_AMPLITUDES && which != THZ_BUF_PHASES && which != THZ_BUF_DATA && which != THZ_BUF_RAW)
-        return fail(ctx, THZ_ERR_INVALID, "principal components are taken of THZ_BUF_AMPLITUDES, _PHASES, _DATA or _RAW");
+        return fail(ctx, THZ_ERR_INVALID, of + "the matrix is THZ_BUF_AMPLITUDES, _PHASES, _DATA or _RAW");
     size_t len = 0;
     if (which == THZ_BUF_RAW) {
         m->d = s->d_raw;
         m->npix = s->nx * s->ny;
         len = s->nt;
     } else {
-        if (!s->have_outputs) return fail(ctx, THZ_ERR_NOT_READY, "principal components: no recompute has run");
+        if (!s->have_outputs) return fail(ctx, THZ_ERR_NOT_READY, of + "no recompute has run");
         const size_t grid = s->nx_cur * s->ny_cur;
         m->npix = s->out_pix < grid ? s->out_pix : grid;
         // the session's own pointers for the spectra: thz_session_buffer would make the next recompute store every
@@ -50,18 +49,19 @@ int session_matrix(thz_session *s, int which, const thz_pca_cfg *cfg, SessionMat
                                            : static_cast<const float *>(session_buffer_ro(s, THZ_BUF_DATA));
         len = which == THZ_BUF_DATA ? s->nt_out : s->nf_out;
     }
-    if (!m->d) return fail(ctx, THZ_ERR_NOT_READY, "principal components: the cube is not available");
+    if (!m->d) return fail(ctx, THZ_ERR_NOT_READY, of + "the cube is not available");
     if (cfg->count < 1 || cfg->count > THZ_PCA_MAX_LEN || cfg->step < 1
         || (uint64_t)cfg->first + (uint64_t)(cfg->count - 1) * (uint64_t)cfg->step >= (uint64_t)len)
         return fail(ctx, THZ_ERR_INVALID,
-                    "principal components: 1 <= count <= THZ_PCA_MAX_LEN, step >= 1, and the last column inside the row of "
-                        + std::to_string(len));
+                    of + "1 <= count <= THZ_PCA_MAX_LEN, step >= 1, and the last column inside the row of " + std::to_string(len));
     m->d += cfg->first;
     m->L = cfg->count;
     m->row_stride = len;
     m->col_step = cfg->step;
     return THZ_OK;
 }
+
+namespace {
 
 bool bad_k(const thz_pca_cfg *cfg)
 {
@@ -145,7 +145,7 @@ int thz_session_pca_sums(thz_session *s, int which, const thz_pca_cfg *cfg, doub
     if (int rc = use_device(ctx)) return rc;
     if (!cfg) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca_sums: cfg is NULL");
     SessionMatrix m;
-    if (int rc = session_matrix(s, which, cfg, &m)) return rc;
+    if (int rc = session_matrix(s, which, cfg, "principal components", &m)) return rc;
     return thz_pca_sums(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, cfg->d_mask, sum, count);
 }
 
@@ -156,7 +156,7 @@ int thz_session_pca_gram(thz_session *s, int which, const thz_pca_cfg *cfg, cons
     if (int rc = use_device(ctx)) return rc;
     if (!cfg) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca_gram: cfg is NULL");
     SessionMatrix m;
-    if (int rc = session_matrix(s, which, cfg, &m)) return rc;
+    if (int rc = session_matrix(s, which, cfg, "principal components", &m)) return rc;
     return thz_pca_gram(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, cfg->d_mask, mu, gram);
 }
 
@@ -167,7 +167,7 @@ int thz_session_pca_project(thz_session *s, int which, const thz_pca_cfg *cfg, c
     if (int rc = use_device(ctx)) return rc;
     if (!cfg || !components) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca_project: a required pointer is NULL");
     SessionMatrix m;
-    if (int rc = session_matrix(s, which, cfg, &m)) return rc;
+    if (int rc = session_matrix(s, which, cfg, "principal components", &m)) return rc;
     if (bad_k(cfg)) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca_project: 1 <= n_components <= min(count, THZ_PCA_MAX_COMPONENTS)");
     const size_t K = (size_t)cfg->n_components;
     // [scores: (K, npix) | components: (K, L) | mean: L]
@@ -201,7 +201,7 @@ int thz_session_pca(thz_session *s, int which, const thz_pca_cfg *cfg, thz_pca_o
     if (!cfg || !out) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca: a required pointer is NULL");
     *out = thz_pca_out{};
     SessionMatrix m;
-    if (int rc = session_matrix(s, which, cfg, &m)) return rc;
+    if (int rc = session_matrix(s, which, cfg, "principal components", &m)) return rc;
     if (bad_k(cfg)) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca: 1 <= n_components <= min(count, THZ_PCA_MAX_COMPONENTS)");
     const size_t L = m.L;
     const int K = cfg->n_components;

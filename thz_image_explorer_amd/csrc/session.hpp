@@ -80,6 +80,11 @@ struct thz_session {
     float *d_pca = nullptr;
     size_t pca_cap = 0;                        // floats allocated
     size_t pca_pix = 0, pca_k = 0, pca_len = 0;  // pixels, components and columns of the last call; 0 pixels: absent
+    // k-means of the last thz_session_cluster / _cluster_step (cluster_api.cpp):
+    // d_cluster = [labels: cluster_pix int32 | dist2: cluster_pix f32 | centroids: (cluster_k, cluster_len) f32]
+    float *d_cluster = nullptr;
+    size_t cluster_cap = 0;                                  // 4-byte words allocated
+    size_t cluster_pix = 0, cluster_k = 0, cluster_len = 0;  // of the last step; 0 pixels: absent
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;
@@ -137,6 +142,15 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
 // thz_session_buffer for readers inside the library: hands out no right to write, so the session keeps what it knows
 // of its spectrum's zeros
 const void *session_buffer_ro(thz_session *s, int which);
+// What `which` (THZ_BUF_AMPLITUDES, _PHASES, _DATA, _RAW) and the columns of cfg name in a session (pca_api.cpp): the
+// strided matrix the PCA and cluster kernels read, or the error, whose message `what` starts
+struct SessionMatrix {
+    const float *d = nullptr;
+    size_t npix = 0, L = 0, row_stride = 0, col_step = 0;
+};
+int session_matrix(thz_session *s, int which, const thz_pca_cfg *cfg, const char *what, SessionMatrix *m);
+// the argument rules of every call on such a matrix: the reason for THZ_ERR_INVALID, or null
+const char *pca_view_error(size_t L, const float *d_x, size_t row_stride, size_t col_step);
 // The extended (re-laid) traces of a tilted chain that ran as one launch: the whole cube into d_tilt (and d_src) when
 // it is not there yet — for the regions of interest's source sums; never on the recompute path of a session without
 // regions.  A no-op for every other chain.

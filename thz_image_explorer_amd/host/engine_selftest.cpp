@@ -324,6 +324,35 @@ int main(int argc, char **argv)
             CHECK(worst_ev < 1e-5, "pca over two slabs == over one (eigenvalues)");
             CHECK(worst_s < 1e-3 * big_s, "pca over two slabs == over one (leading score image)");
         }
+        {
+            // k-means of the resident amplitudes, on one slab and on two: the slabs' sums are added in f64 and the
+            // farthest pixel is taken over both, so the two runs seed, iterate and label alike
+            thz_cluster_cfg cc{};
+            cc.first = 4; cc.count = 40; cc.step = 2; cc.n_clusters = 3; cc.init = 1; cc.max_iter = 20;
+            std::vector<uint8_t> mask((size_t)c.nx * (size_t)c.ny, 1);
+            for (size_t i = 0; i < mask.size(); i += 7) mask[i] = 0;
+            thz_cluster_out o1{}, o2{};
+            std::vector<int32_t> l1, l2;
+            std::vector<float> d1, d2, m1, m2;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0;
+            CHECK(eng.cluster(THZ_BUF_AMPLITUDES, cc, mask, o1, l1, d1, m1, gx1, gy1), "cluster on one slab");
+            CHECK(eng2.cluster(THZ_BUF_AMPLITUDES, cc, mask, o2, l2, d2, m2, gx2, gy2), "cluster on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1, "cluster: the whole grid");
+            CHECK(l1.size() == gx1 * gy1 && l2.size() == l1.size() && d1.size() == l1.size() && m1.size() == 120 && m2.size() == 120, "cluster: sizes");
+            CHECK(o1.count == mask.size() - (mask.size() + 6) / 7 && o2.count == o1.count, "cluster: the unmasked pixels, bit for bit");
+            CHECK(o1.iterations >= 2 && o1.iterations == o2.iterations && o1.converged == o2.converged, "cluster: the same steps");
+            CHECK(o1.counts[0] + o1.counts[1] + o1.counts[2] == o1.count && o1.counts[0] > 0, "cluster: counts add up");
+            CHECK(l1 == l2, "cluster over two slabs == over one (labels)");
+            double worst_m = 0.0, worst_d = 0.0;
+            for (size_t i = 0; i < m1.size(); ++i) worst_m = std::max(worst_m, (double)std::fabs(m1[i] - m2[i]) / std::max((double)std::fabs(m1[i]), 1e-30));
+            for (size_t i = 0; i < d1.size(); ++i) worst_d = std::max(worst_d, (double)std::fabs(d1[i] - d2[i]) / std::max((double)d1[i], 1e-30));
+            std::printf("cluster: %d steps, converged %d, counts %llu %llu %llu, inertia %.6g; two slabs against one: centroids %.3g, distances %.3g (relative)\n",
+                        o1.iterations, o1.converged, (unsigned long long)o1.counts[0], (unsigned long long)o1.counts[1],
+                        (unsigned long long)o1.counts[2], o1.inertia, worst_m, worst_d);
+            CHECK(worst_m <= 1e-6, "cluster over two slabs == over one (centroids)");
+            CHECK(worst_d <= 1e-4, "cluster over two slabs == over one (distances)");
+            CHECK(std::fabs(o1.inertia - o2.inertia) <= 1e-5 * o1.inertia, "cluster over two slabs == over one (inertia)");
+        }
         small_bank(q.filter_by("Deconvolution"));
         q.filters_active[q.filter_chain[q.index_of("Deconvolution")]] = true;
         q.update_filter(q.index_of("Deconvolution"));

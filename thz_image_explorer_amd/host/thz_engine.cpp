@@ -2,6 +2,7 @@
 // file in the reference's language.
 #include "thz_engine.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -546,6 +547,145 @@ bool GpuEngine::pca(int which, const thz_pca_cfg &cfg, const std::vector<uint8_t
         ok = thz_session_pca_project(s, which, &cfgs[(size_t)i], mu, components.data()) == THZ_OK;
         for (size_t c = 0; ok && c < K; ++c)  // a member's scores are component-major over ITS pixels
             ok = thz_session_download(s, THZ_BUF_PCA_SCORES, c * mine, mine, scores.data() + c * npix + at) == THZ_OK;
+        at += mine;
+    }
+    release();
+    return ok;
+}
+bool GpuEngine::cluster(int which, const thz_cluster_cfg &cfg, const std::vector<uint8_t> &mask, thz_cluster_out &out,
+                        std::vector<int32_t> &labels, std::vector<float> &dist2, std::vector<float> &centroids, size_t &gx, size_t &gy)
+{
+    gx = gy = 0;
+    out = thz_cluster_out{};
+    if (!session_ || cfg.count < 1 || cfg.count > THZ_PCA_MAX_LEN || cfg.n_clusters < 1 || cfg.n_clusters > THZ_CLUSTER_MAX
+        || (cfg.init != 0 && cfg.init != 1) || cfg.max_iter < 1 || cfg.max_iter > 1000 || (cfg.init == 0 && !cfg.centroids)
+        || (which == THZ_BUF_PCA_SCORES && !mask.empty()))
+        return false;
+    if (which != THZ_BUF_RAW && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &rows[(size_t)i]);
+            gy = ny;
+        } else {
+            thz_session_grid(thz_group_session_member(session_, i), &rows[(size_t)i], &gy, nullptr, nullptr);
+        }
+        gx += rows[(size_t)i];
+    }
+    const size_t L = cfg.count, K = (size_t)cfg.n_clusters, npix = gx * gy;
+    if (!mask.empty() && mask.size() != npix) return false;
+    // every member's rows of the mask on that member's device, for the length of this call
+    std::vector<void *> d_mask((size_t)members, nullptr);
+    auto release = [&]() {
+        for (int i = 0; i < members; ++i)
+            if (d_mask[(size_t)i]) thz_free(thz_group_ctx(group_, i), d_mask[(size_t)i]);
+    };
+    std::vector<thz_cluster_cfg> cfgs((size_t)members, cfg);
+    std::vector<size_t> pix((size_t)members, 0);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        const size_t mine = pix[(size_t)i] = rows[(size_t)i] * gy;
+        cfgs[(size_t)i].d_mask = nullptr;
+        if (!mask.empty() && mine) {
+            thz_ctx *ctx = thz_group_ctx(group_, i);
+            if (thz_malloc(ctx, &d_mask[(size_t)i], mine) != THZ_OK || thz_memcpy_h2d(ctx, d_mask[(size_t)i], mask.data() + at, mine) != THZ_OK) {
+                release();
+                return false;
+            }
+            cfgs[(size_t)i].d_mask = static_cast<const uint8_t *>(d_mask[(size_t)i]);
+        }
+        at += mine;
+    }
+    // one step on every member with k rows of `cent`, added in member order; far: the global index, npix for none
+    std::vector<double> sums(K * L), part(K * L);
+    uint64_t counts[THZ_CLUSTER_MAX], changed = 0, far = 0;
+    double inertia = 0.0;
+    auto step = [&](const float *cent, size_t k, bool reset, bool want_sums) {
+        std::fill(sums.begin(), sums.end(), 0.0);
+        std::fill(counts, counts + THZ_CLUSTER_MAX, (uint64_t)0);
+        inertia = 0.0;
+        changed = 0;
+        far = npix;
+        float best = -1.0f;
+        size_t before = 0;
+        for (int i = 0; i < members; ++i) {
+            const size_t mine = pix[(size_t)i];
+            if (!mine) continue;
+            thz_session *s = thz_group_session_member(session_, i);
+            thz_cluster_cfg c = cfgs[(size_t)i];
+            c.n_clusters = (int32_t)k;
+            c.init = reset ? 1 : 0;
+            uint64_t n[THZ_CLUSTER_MAX] = {0}, ch = 0, f = 0;
+            double e = 0.0;
+            if (thz_session_cluster_step(s, which, &c, cent, want_sums ? part.data() : nullptr, n, &e, &ch, &f) != THZ_OK) return false;
+            for (size_t j = 0; want_sums && j < k * L; ++j) sums[j] += part[j];
+            for (size_t j = 0; j < k; ++j) counts[j] += n[j];
+            inertia += e;
+            changed += ch;
+            if (f < mine) {
+                float v = 0.0f;
+                if (thz_session_download(s, THZ_BUF_CLUSTER_DIST, (size_t)f, 1, &v) != THZ_OK) return false;
+                if (v > best) {  // members ascend in the global index: the first of equal ones stays
+                    best = v;
+                    far = before + f;
+                }
+            }
+            before += mine;
+        }
+        return true;
+    };
+    auto row = [&](uint64_t p, float *dst) {
+        for (int i = 0; i < members; ++i) {
+            if (p < pix[(size_t)i]) return thz_session_cluster_row(thz_group_session_member(session_, i), which, &cfgs[(size_t)i], p, dst) == THZ_OK;
+            p -= pix[(size_t)i];
+        }
+        return false;
+    };
+    centroids.assign(K * L, 0.0f);
+    std::vector<float> next(K * L, 0.0f);
+    bool ok = npix > 0;
+    if (ok && cfg.init == 0) {
+        std::memcpy(centroids.data(), cfg.centroids, K * L * sizeof(float));
+    } else if (ok) {
+        // farthest-first: the mean from the sums about the zero vector, then the farthest pixel each time
+        ok = step(next.data(), 1, true, true) && counts[0] > 0;
+        for (size_t j = 0; ok && j < L; ++j) next[j] = (float)(sums[j] / (double)counts[0]);
+        for (size_t k = 0; ok && k < K; ++k) {
+            ok = step(k ? centroids.data() : next.data(), k ? k : 1, true, false);
+            if (!ok) break;
+            if (far >= npix) {
+                ok = k > 0;
+                if (ok) std::memcpy(centroids.data() + k * L, centroids.data() + (k - 1) * L, L * sizeof(float));
+            } else {
+                ok = row(far, centroids.data() + k * L);
+            }
+        }
+    }
+    for (int it = 1; ok && it <= cfg.max_iter; ++it) {
+        ok = step(centroids.data(), K, it == 1, true);
+        if (!ok) break;
+        out.iterations = it;
+        out.converged = changed == 0;
+        if (out.converged || it == cfg.max_iter) break;
+        ok = thz_host_cluster_update(sums.data(), counts, (int)K, L, centroids.data(), next.data()) == THZ_OK;
+        centroids.swap(next);
+    }
+    out.inertia = inertia;
+    for (size_t c = 0; ok && c < K; ++c) {
+        out.counts[c] = counts[c];
+        out.count += counts[c];
+    }
+    labels.assign(npix, -1);
+    dist2.assign(npix, 0.0f);
+    at = 0;
+    for (int i = 0; ok && i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = pix[(size_t)i];
+        if (!mine) continue;
+        ok = thz_session_download(s, THZ_BUF_CLUSTER_LABELS, 0, mine, labels.data() + at) == THZ_OK
+             && thz_session_download(s, THZ_BUF_CLUSTER_DIST, 0, mine, dist2.data() + at) == THZ_OK;
         at += mine;
     }
     release();

@@ -100,6 +100,18 @@ public:
     // scores: (n_components, gx, gy); components: (n_components, count); mean: (count), zeros when cfg.center == 0
     bool pca(int which, const thz_pca_cfg &cfg, const std::vector<uint8_t> &mask, thz_pca_out &out, std::vector<float> &scores,
              std::vector<float> &components, std::vector<float> &mean, size_t &gx, size_t &gy);
+    // k-means of everything this process holds: clustering is not pixel-independent, so
+    // thz_session_cluster_step runs on each local member and the members' sums, counts, inertia and changed are added here
+    // in member order (f64); the farthest pixel is the largest THZ_BUF_CLUSTER_DIST entry among the members' candidates,
+    // the lowest global index winning a tie, and thz_session_cluster_row fetches its row; thz_host_cluster_update runs
+    // once per step, and every member iterates with the common centroids.  The mean the seeding starts from is the sum of
+    // a K = 1 step about the zero vector (rows with a NaN are left out of it).  which: what thz_session_cluster takes;
+    // THZ_BUF_PCA_SCORES means the score images of the last pca() of the recompute's grid and takes no mask.
+    // cfg.d_mask is not read: mask is empty or one byte per pixel of the whole (gx, gy) grid.  Every member's
+    // THZ_BUF_CLUSTER_LABELS / _DIST / _CENTROIDS stay resident.
+    // labels, dist2: (gx, gy); centroids: (n_clusters, count)
+    bool cluster(int which, const thz_cluster_cfg &cfg, const std::vector<uint8_t> &mask, thz_cluster_out &out,
+                 std::vector<int32_t> &labels, std::vector<float> &dist2, std::vector<float> &centroids, size_t &gx, size_t &gy);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
