@@ -135,7 +135,8 @@ __device__ __forceinline__ void vox_load(const float *__restrict__ src, int nt, 
 //    summation of the real taps;
 //  * WIDE = true: any radius, one LDS read per tap and output.
 // Out-of-range taps are skipped by the reference (threed_plot.rs:112); reading a
-// zero adds +0.
+// zero adds +0.  (Not for an infinite sample under a zero tap of the padded vector:
+// below radius kVoxPad such a sample spreads NaN kVoxPad samples wide, not radius.)
 template <int NQ, bool VEC, bool WIDE>
 __global__ __launch_bounds__(256) void k_voxel_opacity(size_t npix, int nt, const float *__restrict__ data,
                                                        VoxelTaps taps, const float *__restrict__ wide_taps,
@@ -225,8 +226,10 @@ __global__ __launch_bounds__(256) void k_voxel_opacity(size_t npix, int nt, cons
         mn = wave_min(mn);
         // threed_plot.rs:181-199: whole line zero below the opacity threshold or when flat
         const bool keep = !(mx < opacity_threshold) && fabsf(mx - mn) > 1e-6f;
-        const float range = mx - mn;
-        const float inv = div_rn(1.0f, range);
+        // a line with an infinite sample has range = inf and inv = 0: the residual of vox_div would be
+        // inf * 0.  With the largest finite divisor it is n, and the quotient n * 0 like the reference's n / inf
+        const float range = fminf(mx - mn, 3.402823466e+38f);
+        const float inv = div_rn(1.0f, mx - mn);
         float *dst = out + trace * (size_t)nt;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -258,11 +261,16 @@ static void launch_voxel_opacity_t(hipStream_t st, size_t npix, int nt, const fl
                                    float opacity_threshold, float *out)
 {
     const int pad = WIDE ? ((radius + 3) & ~3) : kVoxPad;
-    const int wpb = 4;
-    const size_t lds = (size_t)wpb * (NQ * 256 + 2 * pad) * sizeof(float);
+    constexpr size_t kLdsLimit = 160 * 1024;  // of a CU, and the most one block may ask for
+    const size_t slice = (size_t)(NQ * 256 + 2 * pad) * sizeof(float);
+    // 4 waves per block, fewer where the slices of a wide radius would not fit; one always fits
+    // (nt <= 8192, radius <= 4096: 64 KiB)
+    int wpb = 4;
+    while (wpb > 1 && wpb * slice > kLdsLimit) wpb >>= 1;
+    const size_t lds = wpb * slice;
     size_t blocks = (npix + wpb - 1) / wpb;
     // persistent-ish grid: enough blocks for every CU's LDS, the waves stride over the traces
-    const size_t per_cu = lds ? (160 * 1024) / lds : 8;
+    const size_t per_cu = kLdsLimit / lds;
     const size_t cap = 256 * (per_cu ? (per_cu > 8 ? 8 : per_cu) : 1);
     if (blocks > cap) blocks = cap;
     if (blocks == 0) return;
