@@ -643,6 +643,58 @@ int thz_cluster_step(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size
 int thz_host_cluster_update(const double *sums, const uint64_t *counts, int K, size_t L,
                             const float *previous /* K x L */, float *centroids /* K x L */);
 
+/* ------------------------------------------------------------------ */
+/* Sparse deconvolution: overlapping echoes (K21)      */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  thz_echo_map finds separated pulses; two surfaces closer than a pulse width give one
+ * merged wavelet.  Here every trace is written as y = h * x + noise with h the reference pulse and x a sparse spike
+ * train, and 1/2 |y - H x|^2 + lam |x|_1 is minimised by iterative shrinkage (ISTA, or FISTA with momentum): the spikes
+ * of x are the echoes.  All arithmetic is f32.
+ *
+ * y is one trace x[0 .. nt), h[0 .. P) the taps, c the centre tap: a spike at sample m puts h[c] at sample m.  With
+ * T[i][m] = h[i + c - m], zero outside 0 <= i + c - m < P:
+ *   (H z)[i]   = sum over m = 0 .. nt-1 of T[i][m] z[m]
+ *   (H^T r)[j] = sum over i = 0 .. nt-1 of T[i][j] r[i]
+ * each ONE fmaf chain from +0.0f in ascending order of the index of the vector it reads, acc = fmaf(T, v, acc); terms
+ * with T = 0 may be skipped or executed (for finite data the value is the same).
+ *   threshold  g0 = H^T y, gmax = max_j |g0[j]|, lam = fmaxf(rel_lambda * gmax, min_lambda), th = step * lam (one f32
+ *              product each)
+ *   start      x = z = 0
+ *   iteration n = 0 .. n_iter-1:  r = y - H z;  g = H^T r;  v = fmaf(step, g, z);  a = fabsf(v) - th;
+ *              xn = a > 0 ? copysignf(a, v) : +0.0f;  z = xn (accelerate == 0) or fmaf(beta[n], xn - x, xn)
+ *              (accelerate == 1);  x = xn
+ *   momentum   on the host in double: t_0 = 1, t_{n+1} = (1 + sqrt(1 + 4 t_n^2)) / 2, beta[n] = (float)((t_n - 1) /
+ *              t_{n+1}); one function makes the table for the device (uploaded once per call) and for the host twin.
+ * d_out (npix, nt) f32 is x after n_iter iterations (all zeros for n_iter == 0); d_resid (npix) f32 or NULL is
+ * sum_i (y - H x)[i]^2, in any order of summation; d_nnz (npix) int32 or NULL the number of x[i] != 0.  d_out == d_data
+ * (in place) is allowed; any other overlap is undefined.  A trace with a non-finite sample has unspecified values in
+ * its own row and affects no other row; subnormal values are outside the definition.
+ * THZ_ERR_INVALID, before any launch or allocation, for anything outside the limits below, a non-finite tap, nt == 0 or
+ * nt > THZ_SPARSE_MAX_NT, or a NULL required pointer (all but d_resid and d_nnz); npix == 0 is a no-op.  d_data needs
+ * 4-byte alignment only.  The cube is read once and written once whatever n_iter: one wave per trace keeps y, z, r and
+ * x in LDS.  Time under THZ_STAGE_ECHO.
+ *
+ * thz_host_sparse_trace is plain C++ with the same chains, no GPU and no context: for finite data it equals the device
+ * bit for bit, -0 and +0 compared as numbers.  y and x may be the same vector.
+ * thz_host_sparse_kernel cuts the taps out of a reference pulse: k0 = the index of the largest |ref|, the lowest index
+ * on ties (thz_host_echo_trace with one rank in mode 0); taps[k] = ref[k0 - center + k], zero outside [0, nref);
+ * *step = (float)(1 / (sum |taps|)^2) in double — (sum |h|)^2 >= |H|^2 by Young's inequality, so this step converges.
+ * THZ_ERR_INVALID when every tap is zero or one is not finite. */
+#define THZ_SPARSE_MAX_TAPS 256
+#define THZ_SPARSE_MAX_NT   4608   /* a 4096-sample scan and its tilt; z, r, x, y of one trace with their halos fit a CU's LDS */
+#define THZ_SPARSE_MAX_ITER 4096
+typedef struct thz_sparse_cfg {
+    int32_t n_taps, center;      /* P in 1..THZ_SPARSE_MAX_TAPS, c in 0..P-1 */
+    int32_t n_iter, accelerate;  /* 0..THZ_SPARSE_MAX_ITER; 0 ISTA, 1 FISTA */
+    float step;                  /* finite, > 0; converges for step <= 1/||H||^2 */
+    float rel_lambda, min_lambda;/* finite, >= 0 */
+} thz_sparse_cfg;
+int thz_sparse_deconv(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data, const float *taps /* P host */,
+                      const thz_sparse_cfg *cfg, float *d_out, float *d_resid, int32_t *d_nnz);
+int thz_host_sparse_trace(const float *y, size_t nt, const float *taps, const thz_sparse_cfg *cfg,
+                          float *x, float *resid, int32_t *nnz);
+int thz_host_sparse_kernel(const float *ref, size_t nref, int n_taps, int center, float *taps, float *step);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -747,7 +799,10 @@ enum {
     THZ_BUF_PCA_MEAN = 26,    /* (L) f32; zeros when the call did not centre */
     THZ_BUF_CLUSTER_LABELS = 27, /* (npix) int32 of the last thz_session_cluster / _cluster_step; -1: every distance NaN */
     THZ_BUF_CLUSTER_DIST = 28,   /* (npix) f32: squared distance to the pixel's centroid */
-    THZ_BUF_CLUSTER_CENTROIDS = 29 /* (K, L) f32: the centroids the labels belong to, one mean row per cluster */
+    THZ_BUF_CLUSTER_CENTROIDS = 29, /* (K, L) f32: the centroids the labels belong to, one mean row per cluster */
+    THZ_BUF_SPARSE = 30,       /* (npix, nt_src) f32: the spike trains of the last thz_session_sparse_deconv */
+    THZ_BUF_SPARSE_RESID = 31, /* (npix) f32: sum of (y - H x)^2 per trace */
+    THZ_BUF_SPARSE_NNZ = 32    /* (npix) int32: spikes per trace */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -876,6 +931,18 @@ int thz_session_optical_maps(thz_session *s, const float *ref_amp, const float *
  * slabs' maps are the whole grid's rows. */
 int thz_session_echo_map(thz_session *s, int which, const thz_echo_cfg *cfg);
 int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg);
+
+/* thz_sparse_deconv on a resident cube: `which` = THZ_BUF_RAW or THZ_BUF_DATA exactly as for thz_session_peak_map (the
+ * same grids, the same THZ_ERR_NOT_READY and THZ_ERR_INVALID cases).  Fills the resident buffers THZ_BUF_SPARSE
+ * (npix, nt of that cube) / _SPARSE_RESID (npix f32) / _SPARSE_NNZ (npix int32) (thz_session_buffer,
+ * thz_session_download with pix0 / npix in pixels; absent until the first call, and again after an upload).  The
+ * session remembers the grid and time axis they belong to: thz_session_peak_map, thz_session_echo_map,
+ * thz_session_estimate_tilt and thz_group_session_estimate_tilt accept `which` = THZ_BUF_SPARSE and then run on the spike
+ * trains (THZ_ERR_NOT_READY before a sparse call), so thz_session_layer_map turns a thin coating's two spikes into a
+ * thickness image that reaches thz_session_optical_maps without leaving the device.
+ * A group has no form of its own: call this on thz_group_session_member(gs, i); every pixel is independent, so the
+ * slabs' spike trains are the whole grid's rows. */
+int thz_session_sparse_deconv(thz_session *s, int which, const float *taps, const thz_sparse_cfg *cfg);
 
 /* Principal components of a resident cube.  `which` names the matrix: THZ_BUF_AMPLITUDES or THZ_BUF_PHASES (columns
  * are bins, nf = nt_out / 2 + 1 of them), THZ_BUF_DATA (samples, nt_out) — all three on the last recompute's grid, as

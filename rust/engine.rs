@@ -90,6 +90,8 @@ pub struct GpuEngine {
     echo_rows: Vec<usize>,
     echo_gy: usize,
     echo_k: usize,
+    sparse_rows: Vec<usize>,
+    sparse_gy: usize,
 }
 
 // the raw handles are only touched under the Mutex around the engine
@@ -109,7 +111,8 @@ impl GpuEngine {
         pending.scale_factor = 1;
         pending.want_means = 1;
         GpuEngine { group, session: ptr::null_mut(), pending, dirty_from: 1, nx: 0, ny: 0, nt: 0, fd_real: vec![], fd_cmask: vec![],
-                    plugins_dirty: true, rois: vec![], rois_dirty: false, echo_rows: vec![], echo_gy: 0, echo_k: 0 }
+                    plugins_dirty: true, rois: vec![], rois_dirty: false, echo_rows: vec![], echo_gy: 0, echo_k: 0,
+                    sparse_rows: vec![], sparse_gy: 0 }
     }
 
     pub fn available(&self) -> bool { !self.group.is_null() }
@@ -415,21 +418,26 @@ impl GpuEngine {
 
     /// The `cfg.n_echoes` strongest separated pulses of every trace this process holds (`thz_session_echo_map` on each
     /// local member, slab after slab: every pixel is independent), of the raw cube (`which = THZ_BUF_RAW`) or of the
-    /// chain's final traces (`THZ_BUF_DATA`; whatever the walk has recorded is flushed first).
+    /// chain's final traces (`THZ_BUF_DATA`; whatever the walk has recorded is flushed first), or of the spike trains of
+    /// the last `sparse_deconv` (`THZ_BUF_SPARSE`, on the grid of the cube they were taken of).
     /// -> (index, offset, value: (n_echoes, gx, gy), rank-major with index -1 for a rank that was not found;
     /// count: (gx, gy); gx; gy)
     pub fn echo_map(&mut self, which: c_int, cfg: &ThzEchoCfg) -> Option<(Vec<i32>, Vec<f32>, Vec<f32>, Vec<i32>, usize, usize)> {
         self.echo_k = 0;
-        if self.session.is_null() || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) { return None; }
+        if self.session.is_null() || (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_SPARSE) { return None; }
         if which == THZ_BUF_DATA && !self.flush() { return None; }
         unsafe {
             let members = thz_group_local_count(self.group);
+            if which == THZ_BUF_SPARSE && self.sparse_rows.len() != members as usize { return None; } // no sparse_deconv has run
             self.echo_rows = vec![0usize; members as usize];
             let (mut gx, mut gy) = (0usize, 0usize);
             for i in 0..members {
                 let s = thz_group_session_member(self.session, i);
                 if thz_session_echo_map(s, which, cfg) != THZ_OK { return None; }
-                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                if which == THZ_BUF_SPARSE { // the grid of the cube the spike trains were taken of
+                    self.echo_rows[i as usize] = self.sparse_rows[i as usize];
+                    gy = self.sparse_gy;
+                } else if which == THZ_BUF_RAW { // the member's slab of the raw grid
                     let mut x0 = 0usize;
                     thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut self.echo_rows[i as usize]);
                     gy = self.ny;
@@ -458,6 +466,55 @@ impl GpuEngine {
             self.echo_gy = gy;
             self.echo_k = k;
             Some((index, offset, value, count, gx, gy))
+        }
+    }
+
+    /// Sparse deconvolution of every trace this process holds (`thz_session_sparse_deconv` on each local
+    /// member, slab after slab: every pixel is independent), of the raw cube (`which = THZ_BUF_RAW`) or of the chain's
+    /// final traces (`THZ_BUF_DATA`; whatever the walk has recorded is flushed first).  `taps`: `cfg.n_taps` values, e.g.
+    /// what `thz_host_sparse_kernel` cuts out of a reference pulse.  Every member's `THZ_BUF_SPARSE / _SPARSE_RESID /
+    /// _SPARSE_NNZ` stay resident: `echo_map(THZ_BUF_SPARSE, ..)` and `layer_map` then turn the spikes of a thin coating
+    /// into its thickness.
+    /// -> (x: (gx, gy, nt_src) spike trains; resid, nnz: (gx, gy); gx; gy; nt_src)
+    pub fn sparse_deconv(&mut self, which: c_int, taps: &[f32], cfg: &ThzSparseCfg) -> Option<(Vec<f32>, Vec<f32>, Vec<i32>, usize, usize, usize)> {
+        self.sparse_rows.clear();
+        if self.session.is_null() || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) || cfg.n_taps < 1 || taps.len() != cfg.n_taps as usize { return None; }
+        if which == THZ_BUF_DATA && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy, mut nt_src) = (0usize, 0usize, 0usize);
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                if thz_session_sparse_deconv(s, which, taps.as_ptr(), cfg) != THZ_OK { return None; }
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut rows[i as usize]);
+                    gy = self.ny;
+                    nt_src = self.nt;
+                } else {
+                    thz_session_grid(s, &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                    nt_src = thz_session_nt_out(s);
+                }
+                gx += rows[i as usize];
+            }
+            let npix = gx * gy;
+            let (mut x, mut resid, mut nnz) = (vec![0f32; npix * nt_src], vec![0f32; npix], vec![0i32; npix]);
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                if thz_session_download(s, THZ_BUF_SPARSE, 0, mine, x.as_mut_ptr().add(at * nt_src) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_SPARSE_RESID, 0, mine, resid.as_mut_ptr().add(at) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_SPARSE_NNZ, 0, mine, nnz.as_mut_ptr().add(at) as *mut c_void) != THZ_OK {
+                    return None;
+                }
+                at += mine;
+            }
+            self.sparse_rows = rows;
+            self.sparse_gy = gy;
+            Some((x, resid, nnz, gx, gy, nt_src))
         }
     }
 

@@ -19,5 +19,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       PcaCfg, PcaOut, pca_cfg, host_pca_components, PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN, STAGE_PCA,
                       BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN,
                       ClusterCfg, ClusterOut, cluster_cfg, host_cluster_update, CLUSTER_MAX, CLUSTER_INIT_GIVEN, CLUSTER_INIT_FARTHEST,
-                      BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS)
+                      BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS,
+                      SparseCfg, sparse_cfg, host_sparse_trace, host_sparse_kernel, SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER,
+                      BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ)
 from . import binding  # noqa: F401

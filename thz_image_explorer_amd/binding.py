@@ -119,7 +119,9 @@ BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BU
     BUF_OPT_N, BUF_OPT_ALPHA, BUF_OPT_KAPPA, BUF_OPT_WRAPS, BUF_OPT_SLOPE, \
     BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY, \
     BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN, \
-    BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS = range(30)
+    BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS, \
+    BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ = range(33)
+SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER = 256, 4608, 4096  # THZ_SPARSE_*: taps, samples and iterations of one call
 OPTICAL_MAX_BANDS = 8
 ECHO_MAX = 4
 PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN = 512, 8, 1024  # THZ_PCA_*: columns, components, products per f32 accumulator
@@ -213,6 +215,16 @@ def cluster_cfg(first, count, step=1, n_clusters=3, init=CLUSTER_INIT_FARTHEST, 
         cfg._centroids = np.ascontiguousarray(centroids, np.float32)
         cfg.centroids = cfg._centroids.ctypes.data
     return cfg
+
+
+class SparseCfg(C.Structure):
+    """thz_sparse_cfg: taps and centre tap, iterations, ISTA (0) or FISTA (1), step and the threshold's two parts"""
+    _fields_ = [("n_taps", C.c_int32), ("center", C.c_int32), ("n_iter", C.c_int32), ("accelerate", C.c_int32),
+                ("step", C.c_float), ("rel_lambda", C.c_float), ("min_lambda", C.c_float)]
+
+
+def sparse_cfg(n_taps, center, n_iter=100, accelerate=True, step=1.0, rel_lambda=0.05, min_lambda=0.0) -> SparseCfg:
+    return SparseCfg(int(n_taps), int(center), int(n_iter), int(accelerate), float(step), float(rel_lambda), float(min_lambda))
 
 
 class ThzError(RuntimeError):
@@ -350,6 +362,10 @@ SYMBOLS = [
     ("thz_session_cluster", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), C.POINTER(ClusterOut)]),
     ("thz_session_cluster_step", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), _P, _P, _P, _P, _P, _P]),
     ("thz_session_cluster_row", C.c_int, [_P, C.c_int, C.POINTER(ClusterCfg), C.c_uint64, _P]),
+    ("thz_sparse_deconv", C.c_int, [_P, _SZ, _SZ, _P, _P, C.POINTER(SparseCfg), _P, _P, _P]),
+    ("thz_host_sparse_trace", C.c_int, [_P, _SZ, _P, C.POINTER(SparseCfg), _P, _P, _P]),
+    ("thz_host_sparse_kernel", C.c_int, [_P, _SZ, C.c_int, C.c_int, _P, _P]),
+    ("thz_session_sparse_deconv", C.c_int, [_P, C.c_int, _P, C.POINTER(SparseCfg)]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -559,6 +575,25 @@ def host_cluster_update(sums, counts, previous):
     return rc, out[:k, :width]
 
 
+def host_sparse_trace(y, taps, cfg: SparseCfg):
+    """thz_host_sparse_trace -> (rc, x f32 (nt), resid, nnz)"""
+    a = np.ascontiguousarray(y, np.float32).ravel()
+    h = np.ascontiguousarray(taps, np.float32).ravel()
+    x = np.zeros(max(a.size, 1), np.float32)
+    resid, nnz = C.c_float(), C.c_int32()
+    rc = load_library().thz_host_sparse_trace(a.ctypes.data, a.size, h.ctypes.data, C.byref(cfg), x.ctypes.data, C.byref(resid),
+                                              C.byref(nnz))
+    return rc, x[:a.size], resid.value, nnz.value
+
+
+def host_sparse_kernel(ref, n_taps, center):
+    """thz_host_sparse_kernel -> (rc, taps f32 (n_taps), step)"""
+    r = np.ascontiguousarray(ref, np.float32).ravel()
+    taps, step = np.zeros(max(int(n_taps), 1), np.float32), C.c_float()
+    rc = load_library().thz_host_sparse_kernel(r.ctypes.data, r.size, int(n_taps), int(center), taps.ctypes.data, C.byref(step))
+    return rc, taps[:max(int(n_taps), 0)], step.value
+
+
 def voxel_cfg_default() -> VoxelCfg:
     cfg = VoxelCfg()
     _rc(load_library().thz_voxel_cfg_default(C.byref(cfg)), "voxel_cfg_default")
@@ -697,7 +732,7 @@ class Session:
     def peak_map(self, which=0, mode=PEAK_ABS):
         """arrival-time maps of THZ_BUF_RAW / THZ_BUF_DATA -> (index int32, offset f32, value f32), each (gx, gy)"""
         self.eng._check(self.eng.lib.thz_session_peak_map(self.h, int(which), int(mode)))
-        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        gx, gy = self._cube_pix(which)
         return tuple(self.download(b, npix=gx * gy).reshape(gx, gy) for b in (BUF_PEAK_INDEX, BUF_PEAK_OFFSET, BUF_PEAK_VALUE))
 
     def estimate_tilt(self, which=0, mode=PEAK_ABS, rel_threshold=0.25):
@@ -728,7 +763,7 @@ class Session:
         """thz_session_echo_map of THZ_BUF_RAW / THZ_BUF_DATA -> (index int32, offset f32, value f32: (n_echoes, gx, gy);
         count int32 (gx, gy))"""
         self.eng._check(self.eng.lib.thz_session_echo_map(self.h, int(which), C.byref(cfg)))
-        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        gx, gy = self._cube_pix(which)
         k = int(cfg.n_echoes)
         self._echo_grid = (k, gx, gy)
         return (*(self.download(b, npix=k * gx * gy).reshape(k, gx, gy) for b in (BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE)),
@@ -741,6 +776,23 @@ class Session:
         k, gx, gy = self._echo_grid
         rows = k - 1 if cfg.mode == LAYER_BETWEEN else 1
         return tuple(self.download(b, npix=rows * gx * gy).reshape(rows, gx, gy) for b in (BUF_LAYER_THICKNESS, BUF_LAYER_DELAY))
+
+    def _cube_pix(self, which):
+        """(gx, gy) of the cube `which` names for the per-trace maps: the raw grid, the last recompute's, or the grid of
+        the cube the spike trains were taken of"""
+        if which == BUF_SPARSE:
+            return self._sparse_grid[:2]
+        return (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+
+    def sparse_deconv(self, which, taps, cfg: "SparseCfg"):
+        """thz_session_sparse_deconv of THZ_BUF_RAW / THZ_BUF_DATA -> (x f32 (gx, gy, nt), resid f32 (gx, gy), nnz int32
+        (gx, gy)); the spike trains stay resident as THZ_BUF_SPARSE"""
+        h = np.ascontiguousarray(taps, np.float32).ravel()
+        self.eng._check(self.eng.lib.thz_session_sparse_deconv(self.h, int(which), h.ctypes.data, C.byref(cfg)))
+        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
+        self._sparse_grid = (gx, gy, self.nt if which == BUF_RAW else self.nt_out)
+        return (self.download(BUF_SPARSE).reshape(gx, gy, -1), self.download(BUF_SPARSE_RESID).reshape(gx, gy),
+                self.download(BUF_SPARSE_NNZ).reshape(gx, gy))
 
     def _pca_pix(self, which):
         gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
@@ -846,6 +898,10 @@ class Session:
             out = np.empty(npix, np.float32)
         elif BUF_CLUSTER_LABELS <= which <= BUF_CLUSTER_CENTROIDS:  # npix: entries of the flattened array, likewise
             out = np.empty(npix, np.int32 if which == BUF_CLUSTER_LABELS else np.float32)
+        elif BUF_SPARSE <= which <= BUF_SPARSE_NNZ:  # pix0 / npix: pixels of the grid the spike trains were taken of
+            gx, gy, nts = getattr(self, "_sparse_grid", (0, 0, 0))
+            npix = max(gx * gy - pix0, 0) if npix is None else npix
+            out = np.empty((npix, nts) if which == BUF_SPARSE else npix, np.int32 if which == BUF_SPARSE_NNZ else np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -1255,6 +1311,13 @@ class Engine:
                                               _dp(dist2), None if sums is None else sums.ctypes.data, counts.ctypes.data,
                                               C.byref(inertia), C.byref(changed), C.byref(far)))
         return (None if sums is None else sums[:k, :n]), counts[:k], inertia.value, changed.value, far.value
+
+    def sparse_deconv(self, npix, nt, data, taps, cfg: "SparseCfg", out, resid=None, nnz=None):
+        """thz_sparse_deconv on device buffers: out (npix, nt) f32 (may be data itself), resid (npix) f32 and nnz (npix)
+        int32 or None"""
+        h = np.ascontiguousarray(taps, np.float32).ravel()
+        self._check(self.lib.thz_sparse_deconv(self.ctx, npix, nt, _dp(data), h.ctypes.data, C.byref(cfg), _dp(out), _dp(resid),
+                                               _dp(nnz)))
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

@@ -38,9 +38,19 @@ int thz_arrival_plane_moments(thz_ctx *ctx, size_t nx, size_t ny, float dx, floa
 int session_cube(thz_session *s, int which, SessionCube *out)
 {
     thz_ctx *ctx = s->ctx;
-    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA)
-        return fail(ctx, THZ_ERR_INVALID, "arrival times are taken of THZ_BUF_RAW or THZ_BUF_DATA");
+    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_SPARSE)
+        return fail(ctx, THZ_ERR_INVALID, "arrival times are taken of THZ_BUF_RAW, THZ_BUF_DATA or THZ_BUF_SPARSE");
     out->d = static_cast<const float *>(session_buffer_ro(s, which));
+    if (which == THZ_BUF_SPARSE) {  // the spike trains, on the grid and axis of the cube they were taken of
+        if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: no spike trains are resident (thz_session_sparse_deconv)");
+        out->nx = s->sparse_nx;
+        out->ny = s->sparse_ny;
+        out->nt = s->sparse_nt;
+        out->dx = s->sparse_dx;
+        out->dy = s->sparse_dy;
+        out->dt_ps = s->sparse_dt_ps;
+        return THZ_OK;
+    }
     if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: the cube is not available (no recompute has run)");
     const bool raw = which == THZ_BUF_RAW;
     const std::vector<float> &time = raw ? s->time : s->time_out;

@@ -85,6 +85,13 @@ struct thz_session {
     float *d_cluster = nullptr;
     size_t cluster_cap = 0;                                  // 4-byte words allocated
     size_t cluster_pix = 0, cluster_k = 0, cluster_len = 0;  // of the last step; 0 pixels: absent
+    // spike trains of the last thz_session_sparse_deconv (sparse_api.cpp), four bytes an entry:
+    // d_sparse = [x: (pixels, sparse_nt) | residual: pixels f32 | non-zeros: pixels int32]
+    float *d_sparse = nullptr;
+    size_t sparse_cap = 0;                                 // entries allocated
+    size_t sparse_nx = 0, sparse_ny = 0, sparse_nt = 0;    // grid and trace length of the cube they were taken of; 0: absent
+    float sparse_dx = 1.0f, sparse_dy = 1.0f;              // ... its pixel pitch
+    double sparse_dt_ps = 0.0;                             // ... and the mean step of its time axis
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;
@@ -184,8 +191,9 @@ int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only);
 int session_roi_finish(thz_session *s, const thz_chain_cfg *cfg, bool data_only);
 size_t session_roi_floats(const thz_session *s);
 void session_roi_free(thz_session *s);
-// peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA) with its grid, trace length and the mean step of
-// its time axis; THZ_ERR_NOT_READY when it is absent
+// peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA, or THZ_BUF_SPARSE: the spike trains, on the grid
+// and time axis of the cube they were taken of) with its grid, trace length and the mean step of its time axis;
+// THZ_ERR_NOT_READY when it is absent
 struct SessionCube {
     const float *d = nullptr;
     size_t nx = 0, ny = 0, nt = 0;

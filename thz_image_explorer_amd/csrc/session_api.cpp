@@ -103,7 +103,7 @@ void thz_session_destroy(thz_session *s)
                     (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out,
                     (void *)s->d_peak_index, (void *)s->d_peak_offset, (void *)s->d_peak_value, (void *)s->d_opt,
                     (void *)s->d_opt_wraps, (void *)s->d_echo, (void *)s->d_layer, (void *)s->d_pca,
-                    (void *)s->d_cluster})
+                    (void *)s->d_cluster, (void *)s->d_sparse})
         if (p) (void)hipFree(p);
     if (s->h_vec) (void)hipHostFree(s->h_vec);
     session_roi_free(s);
@@ -126,6 +126,7 @@ int thz_session_upload(thz_session *s, const float *cube, int subtract_bias)
     s->echo_pix = s->echo_k = s->layer_pix = s->layer_rows = 0;  // ... and the echo and layer maps
     s->pca_pix = s->pca_k = s->pca_len = 0;  // ... and the principal components
     s->cluster_pix = s->cluster_k = s->cluster_len = 0;  // ... and the segmentation
+    s->sparse_nx = s->sparse_ny = s->sparse_nt = 0;  // ... and the spike trains
     if (cube) HIP_TRY(ctx, hipMemcpyAsync(s->d_raw, cube, npix * s->nt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     launch_intensity(ctx->stream, npix, (int)s->nt, s->d_raw, s->d_img, subtract_bias ? 1 : 0);
     if (int rc = check_launch(ctx)) return rc;
@@ -752,6 +753,12 @@ const void *session_buffer_ro(thz_session *s, int which)
         if (!s->cluster_pix) return nullptr;
         return s->d_cluster + (size_t)(which - THZ_BUF_CLUSTER_LABELS) * s->cluster_pix;
     }
+    // the spike trains belong to whichever cube was deconvolved last, the raw one included
+    if (which >= THZ_BUF_SPARSE && which <= THZ_BUF_SPARSE_NNZ) {
+        const size_t pix = s->sparse_nx * s->sparse_ny;
+        if (!pix || !s->sparse_nt) return nullptr;
+        return which == THZ_BUF_SPARSE ? s->d_sparse : s->d_sparse + pix * (s->sparse_nt + (size_t)(which - THZ_BUF_SPARSE_RESID));
+    }
     // Before the first recompute (and between an upload and the next recompute) the output buffers hold
     // nothing a caller may read — and after a scaled recompute they are sized for the smaller grid while
     // the session's grid is the raw one again: absent (NULL / THZ_ERR_NOT_READY) until a recompute has run.
@@ -797,6 +804,7 @@ int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, vo
                              : which == THZ_BUF_PCA_MEAN ? s->pca_len
                              : (which == THZ_BUF_CLUSTER_LABELS || which == THZ_BUF_CLUSTER_DIST) ? s->cluster_pix
                              : which == THZ_BUF_CLUSTER_CENTROIDS ? s->cluster_k * s->cluster_len
+                             : (which >= THZ_BUF_SPARSE && which <= THZ_BUF_SPARSE_NNZ) ? s->sparse_nx * s->sparse_ny
                              : which == THZ_BUF_IMG ? s->nx_cur * s->ny_cur
                                                     : (s->out_pix < s->nx_cur * s->ny_cur ? s->out_pix : s->nx_cur * s->ny_cur);
     switch (which) {
@@ -810,6 +818,8 @@ int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, vo
     case THZ_BUF_LAYER_THICKNESS: case THZ_BUF_LAYER_DELAY: per = 1; break;
     case THZ_BUF_PCA_SCORES: case THZ_BUF_PCA_COMPONENTS: case THZ_BUF_PCA_MEAN: per = 1; break;
     case THZ_BUF_CLUSTER_LABELS: case THZ_BUF_CLUSTER_DIST: case THZ_BUF_CLUSTER_CENTROIDS: per = 1; break;
+    case THZ_BUF_SPARSE: per = s->sparse_nt; break;
+    case THZ_BUF_SPARSE_RESID: case THZ_BUF_SPARSE_NNZ: per = 1; break;
     case THZ_BUF_AVG_FFT: return thz_memcpy_d2h(ctx, dst, base, 2 * s->nf_out * sizeof(float));
     case THZ_BUF_AVG_AMPLITUDES: case THZ_BUF_AVG_PHASES: return thz_memcpy_d2h(ctx, dst, base, s->nf_out * sizeof(float));
     default: return THZ_ERR_INVALID;

@@ -296,6 +296,46 @@ int main(int argc, char **argv)
                   "layer_map over two slabs == over one");
         }
         {
+            // sparse deconvolution of the raw cube, on one slab and on two: every pixel is independent and every sum has
+            // one order, so the slabs' spike trains are the whole grid's rows bit for bit — and so are the echo maps taken
+            // of them
+            std::vector<float> ref((size_t)c.nt), taps(48);
+            for (size_t i = 0; i < ref.size(); ++i) ref[i] = c.raw[i];  // pixel (0, 0)'s trace as the reference pulse
+            thz_sparse_cfg sc{};
+            sc.n_taps = 48; sc.center = 24; sc.n_iter = 25; sc.accelerate = 1; sc.rel_lambda = 0.05f; sc.min_lambda = 0.0f;
+            CHECK(thz_host_sparse_kernel(ref.data(), ref.size(), sc.n_taps, sc.center, taps.data(), &sc.step) == THZ_OK, "sparse kernel from a trace");
+            std::vector<float> x1, x2, r1, r2;
+            std::vector<int32_t> n1, n2;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0, nt1 = 0, nt2 = 0;
+            CHECK(eng.sparse_deconv(THZ_BUF_RAW, taps, sc, x1, r1, n1, gx1, gy1, nt1), "sparse_deconv on one slab");
+            CHECK(eng2.sparse_deconv(THZ_BUF_RAW, taps, sc, x2, r2, n2, gx2, gy2, nt2), "sparse_deconv on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1 && nt1 == (size_t)c.nt && nt2 == nt1, "sparse_deconv: the whole grid");
+            CHECK(x1.size() == gx1 * gy1 * nt1 && r1.size() == gx1 * gy1 && n1.size() == r1.size(), "sparse_deconv: sizes");
+            CHECK(x1.size() == x2.size() && std::memcmp(x1.data(), x2.data(), x1.size() * sizeof(float)) == 0 && n1 == n2
+                      && std::memcmp(r1.data(), r2.data(), r1.size() * sizeof(float)) == 0,
+                  "sparse_deconv over two slabs == over one");
+            // the device against the host function on one trace
+            std::vector<float> hx(nt1);
+            float hr = 0.0f;
+            int32_t hn = 0;
+            std::vector<float> y5(nt1);
+            for (size_t i = 0; i < nt1; ++i) y5[i] = c.raw[5 * nt1 + i] - c.raw[5 * nt1];  // as uploaded: the first sample taken off
+            CHECK(thz_host_sparse_trace(y5.data(), nt1, taps.data(), &sc, hx.data(), &hr, &hn) == THZ_OK, "host sparse trace");
+            bool same = hn == n1[5];
+            for (size_t i = 0; i < nt1; ++i) same = same && hx[i] == x1[5 * nt1 + i];
+            CHECK(same, "sparse_deconv == thz_host_sparse_trace on a trace");
+            size_t spikes = 0;
+            for (int32_t n : n1) spikes += (size_t)n;
+            std::printf("sparse_deconv: %.1f spikes per trace of %zu samples\n", (double)spikes / (double)n1.size(), nt1);
+            thz_echo_cfg ec{};
+            ec.mode = 0; ec.n_echoes = 2; ec.guard = 4; ec.rel_threshold = 0.3f;
+            std::vector<int32_t> i1, i2, c1, c2;
+            std::vector<float> o1, o2, v1, v2;
+            CHECK(eng.echo_map(THZ_BUF_SPARSE, ec, i1, o1, v1, c1, gx1, gy1) && eng2.echo_map(THZ_BUF_SPARSE, ec, i2, o2, v2, c2, gx2, gy2),
+                  "echo_map of the spike trains on one slab and on two");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && i1 == i2 && c1 == c2, "echo_map of the spike trains over two slabs == over one");
+        }
+        {
             // principal components of the resident amplitudes, on one slab and on two: the slabs' sums and Gram matrices
             // are added in f64, so the eigenvalues agree far inside the Gram matrix's own f32 error, and the scores to
             // the f32 rounding of the components

@@ -401,14 +401,18 @@ bool GpuEngine::echo_map(int which, const thz_echo_cfg &cfg, std::vector<int32_t
 {
     gx = gy = 0;
     echo_k_ = 0;
-    if (!session_ || (which != THZ_BUF_RAW && which != THZ_BUF_DATA)) return false;
+    if (!session_ || (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_SPARSE)) return false;
     if (which == THZ_BUF_DATA && !flush()) return false;
     const int members = thz_group_local_count(group_);
+    if (which == THZ_BUF_SPARSE && sparse_rows_.size() != (size_t)members) return false;  // no sparse_deconv has run
     echo_rows_.assign((size_t)members, 0);
     for (int i = 0; i < members; ++i) {
         thz_session *s = thz_group_session_member(session_, i);
         if (thz_session_echo_map(s, which, &cfg) != THZ_OK) return false;
-        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+        if (which == THZ_BUF_SPARSE) {  // the grid of the cube the spike trains were taken of
+            echo_rows_[(size_t)i] = sparse_rows_[(size_t)i];
+            gy = sparse_gy_;
+        } else if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
             size_t x0 = 0;
             thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &echo_rows_[(size_t)i]);
             gy = ny;
@@ -438,6 +442,48 @@ bool GpuEngine::echo_map(int which, const thz_echo_cfg &cfg, std::vector<int32_t
     }
     echo_gy_ = gy;
     echo_k_ = K;
+    return true;
+}
+bool GpuEngine::sparse_deconv(int which, const std::vector<float> &taps, const thz_sparse_cfg &cfg, std::vector<float> &x,
+                              std::vector<float> &resid, std::vector<int32_t> &nnz, size_t &gx, size_t &gy, size_t &nt_src)
+{
+    gx = gy = nt_src = 0;
+    sparse_rows_.clear();
+    if (!session_ || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) || cfg.n_taps < 1 || taps.size() != (size_t)cfg.n_taps) return false;
+    if (which == THZ_BUF_DATA && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        if (thz_session_sparse_deconv(s, which, taps.data(), &cfg) != THZ_OK) return false;
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &rows[(size_t)i]);
+            gy = ny;
+            nt_src = nt;
+        } else {
+            thz_session_grid(s, &rows[(size_t)i], &gy, nullptr, nullptr);
+            nt_src = thz_session_nt_out(s);
+        }
+        gx += rows[(size_t)i];
+    }
+    const size_t npix = gx * gy;
+    x.assign(npix * nt_src, 0.0f);
+    resid.assign(npix, 0.0f);
+    nnz.assign(npix, 0);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = rows[(size_t)i] * gy;
+        if (!mine) continue;
+        if (thz_session_download(s, THZ_BUF_SPARSE, 0, mine, x.data() + at * nt_src) != THZ_OK
+            || thz_session_download(s, THZ_BUF_SPARSE_RESID, 0, mine, resid.data() + at) != THZ_OK
+            || thz_session_download(s, THZ_BUF_SPARSE_NNZ, 0, mine, nnz.data() + at) != THZ_OK)
+            return false;
+        at += mine;
+    }
+    sparse_rows_ = rows;
+    sparse_gy_ = gy;
     return true;
 }
 bool GpuEngine::layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,

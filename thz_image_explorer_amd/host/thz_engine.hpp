@@ -82,7 +82,8 @@ public:
                       std::vector<float> &slope, size_t &gx, size_t &gy);
     // The cfg.n_echoes strongest separated pulses of every trace this process holds (thz_session_echo_map on each local
     // member, slab after slab: every pixel is independent), of the raw cube (which = THZ_BUF_RAW) or of the chain's final
-    // traces (THZ_BUF_DATA; whatever the walk has recorded is flushed first).
+    // traces (THZ_BUF_DATA; whatever the walk has recorded is flushed first), or of the spike trains of the last
+    // sparse_deconv (THZ_BUF_SPARSE, on the grid of the cube they were taken of).
     // index, offset, value: (n_echoes, gx, gy), rank-major with index -1 for a rank that was not found; count: (gx, gy)
     bool echo_map(int which, const thz_echo_cfg &cfg, std::vector<int32_t> &index, std::vector<float> &offset,
                   std::vector<float> &value, std::vector<int32_t> &count, size_t &gx, size_t &gy);
@@ -91,6 +92,14 @@ public:
     // THZ_BUF_LAYER_THICKNESS stays resident: a row of it is a valid d_thickness of thz_session_optical_maps
     bool layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,
                    size_t &gx, size_t &gy);
+    // Sparse deconvolution of every trace this process holds (thz_session_sparse_deconv on each local
+    // member, slab after slab: every pixel is independent), of the raw cube (which = THZ_BUF_RAW) or of the chain's final
+    // traces (THZ_BUF_DATA; whatever the walk has recorded is flushed first).  taps: cfg.n_taps values, e.g. what
+    // thz_host_sparse_kernel cuts out of a reference pulse.  Every member's THZ_BUF_SPARSE / _SPARSE_RESID / _SPARSE_NNZ
+    // stay resident: echo_map(THZ_BUF_SPARSE, ...) and layer_map then turn the spikes of a thin coating into its thickness.
+    // x: (gx, gy, nt_src) spike trains; resid, nnz: (gx, gy)
+    bool sparse_deconv(int which, const std::vector<float> &taps, const thz_sparse_cfg &cfg, std::vector<float> &x,
+                       std::vector<float> &resid, std::vector<int32_t> &nnz, size_t &gx, size_t &gy, size_t &nt_src);
     // Principal components of everything this process holds: the covariance is not pixel-independent, so
     // thz_session_pca_sums and thz_session_pca_gram run on each local member, the members' sums and Gram matrices are
     // added here in member order (f64), thz_host_pca_components runs once, and thz_session_pca_project fills each
@@ -129,6 +138,8 @@ private:
     bool plugins_dirty_ = true;
     std::vector<size_t> echo_rows_;          // the last echo_map: rows per local member, columns and ranks (0: none)
     size_t echo_gy_ = 0, echo_k_ = 0;
+    std::vector<size_t> sparse_rows_;        // the last sparse_deconv: rows per local member (empty: none) and columns
+    size_t sparse_gy_ = 0;
     std::vector<std::pair<std::string, Polygon>> rois_;
     bool rois_dirty_ = false;
 };
