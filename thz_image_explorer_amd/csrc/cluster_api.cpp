@@ -20,51 +20,49 @@ int cluster_matrix(thz_session *s, int which, const thz_cluster_cfg *cfg, Sessio
         columns.step = cfg->step;
         return session_matrix(s, which, &columns, "k-means", m);
     }
-    if (!s->pca_pix || !s->d_pca) return fail(ctx, THZ_ERR_NOT_READY, "k-means: no principal components have been taken");
+    // the resident [scores: (K, npix) | components: (K, L) | mean: L]
+    const ResidentMaps &pca = s->maps[kMapPca];
+    const size_t L = pca.entries(2), K = L ? pca.entries(1) / L : 0, npix = K ? pca.entries(0) / K : 0;
+    if (!npix) return fail(ctx, THZ_ERR_NOT_READY, "k-means: no principal components have been taken");
     if (cfg->count < 1 || cfg->count > THZ_PCA_MAX_LEN || cfg->step < 1
-        || (uint64_t)cfg->first + (uint64_t)(cfg->count - 1) * (uint64_t)cfg->step >= (uint64_t)s->pca_k)
-        return fail(ctx, THZ_ERR_INVALID, "k-means: count >= 1, step >= 1, and the last component inside the " + std::to_string(s->pca_k)
+        || (uint64_t)cfg->first + (uint64_t)(cfg->count - 1) * (uint64_t)cfg->step >= (uint64_t)K)
+        return fail(ctx, THZ_ERR_INVALID, "k-means: count >= 1, step >= 1, and the last component inside the " + std::to_string(K)
                                               + " of the last PCA call");
     // (component, pixel), component-major: a pixel's row has its values npix apart
-    m->d = s->d_pca + (size_t)cfg->first * s->pca_pix;
-    m->npix = s->pca_pix;
+    m->d = pca.ptr(0) + (size_t)cfg->first * npix;
+    m->npix = npix;
     m->L = cfg->count;
     m->row_stride = 1;
-    m->col_step = (size_t)cfg->step * s->pca_pix;
+    m->col_step = (size_t)cfg->step * npix;
     return THZ_OK;
 }
 
 bool bad_k(const thz_cluster_cfg *cfg) { return cfg->n_clusters < 1 || cfg->n_clusters > THZ_CLUSTER_MAX; }
 
 // One step on the session's resident labels and distances; `centroids` (K x L) become the resident centroids.
-// d_cluster = [labels: npix | dist2: npix | centroids: up to THZ_CLUSTER_MAX x THZ_PCA_MAX_LEN]
+// [labels: npix | dist2: npix | centroids: (K, L)], the block sized for THZ_CLUSTER_MAX x THZ_PCA_MAX_LEN centroids so that
+// the steps of one run never move it
 int session_step(thz_session *s, const SessionMatrix &m, const uint8_t *d_mask, const float *centroids, int K, bool reset, double *sums,
                  uint64_t *counts, double *inertia, uint64_t *changed, uint64_t *farthest)
 {
     thz_ctx *ctx = s->ctx;
-    if (s->cluster_pix != m.npix) reset = true;
-    s->cluster_pix = s->cluster_k = s->cluster_len = 0;
-    const size_t need = 2 * m.npix + (size_t)THZ_CLUSTER_MAX * THZ_PCA_MAX_LEN;
-    if (need > s->cluster_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_cluster) (void)hipFree(s->d_cluster);
-        s->d_cluster = nullptr;
-        s->cluster_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_cluster, need * sizeof(float)));
-        s->cluster_cap = need;
-    }
-    int32_t *d_label = reinterpret_cast<int32_t *>(s->d_cluster);
-    float *d_dist2 = s->d_cluster + m.npix;
-    if (reset && m.npix) HIP_TRY(ctx, hipMemsetAsync(d_label, 0xff, m.npix * sizeof(int32_t), ctx->stream));
-    if (int rc = thz_cluster_step(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, d_mask, centroids, K, d_label, d_dist2, sums, counts,
-                                  inertia, changed, farthest))
+    ResidentMaps &r = s->maps[kMapCluster];
+    if (r.entries(0) != m.npix) reset = true;  // no labels of this many pixels are resident
+    if (int rc = maps_begin(ctx, &r, {{m.npix}, {m.npix}, {(size_t)K * m.L}}, 2 * m.npix + (size_t)THZ_CLUSTER_MAX * THZ_PCA_MAX_LEN))
         return rc;
-    if (int rc = thz_memcpy_h2d(ctx, s->d_cluster + 2 * m.npix, centroids, (size_t)K * m.L * sizeof(float))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->cluster_pix = m.npix;
-    s->cluster_k = (size_t)K;
-    s->cluster_len = m.L;
-    return THZ_OK;
+    if (reset && m.npix) HIP_TRY(ctx, hipMemsetAsync(r.ptr(0), 0xff, m.npix * sizeof(int32_t), ctx->stream));
+    if (int rc = thz_cluster_step(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, d_mask, centroids, K, r.ptr<int32_t>(0), r.ptr(1), sums,
+                                  counts, inertia, changed, farthest))
+        return rc;
+    if (int rc = thz_memcpy_h2d(ctx, r.ptr(2), centroids, (size_t)K * m.L * sizeof(float))) return rc;
+    return maps_commit(ctx, &r);
+}
+
+// a run that cannot go on after some of its steps: their labels are no result
+int unfinished(thz_session *s, const char *why)
+{
+    s->maps[kMapCluster].resident = false;
+    return fail(s->ctx, THZ_ERR_INVALID, why);
 }
 
 int fetch_row(thz_ctx *ctx, const SessionMatrix &m, size_t pixel, float *row)
@@ -176,10 +174,7 @@ int thz_session_cluster(thz_session *s, int which, const thz_cluster_cfg *cfg, t
             const float *seen = k ? cent.data() : next.data();
             if (int rc = session_step(s, m, cfg->d_mask, seen, k ? k : 1, true, nullptr, counts, &inertia, &changed, &farthest)) return rc;
             if (farthest >= (uint64_t)m.npix) {
-                if (!k) {
-                    s->cluster_pix = s->cluster_k = s->cluster_len = 0;
-                    return fail(ctx, THZ_ERR_INVALID, "thz_session_cluster: no pixel at a finite distance from the mean");
-                }
+                if (!k) return unfinished(s, "thz_session_cluster: no pixel at a finite distance from the mean");
                 std::memcpy(cent.data() + (size_t)k * L, cent.data() + (size_t)(k - 1) * L, L * sizeof(float));
             } else if (int rc = fetch_row(ctx, m, (size_t)farthest, cent.data() + (size_t)k * L)) {
                 return rc;
@@ -191,10 +186,8 @@ int thz_session_cluster(thz_session *s, int which, const thz_cluster_cfg *cfg, t
         out->iterations = it;
         out->converged = changed == 0;
         if (out->converged || it == cfg->max_iter) break;
-        if (thz_host_cluster_update(sums.data(), counts, K, L, cent.data(), next.data()) != THZ_OK) {
-            s->cluster_pix = s->cluster_k = s->cluster_len = 0;
-            return fail(ctx, THZ_ERR_INVALID, "thz_session_cluster: a cluster's sum is not finite");
-        }
+        if (thz_host_cluster_update(sums.data(), counts, K, L, cent.data(), next.data()) != THZ_OK)
+            return unfinished(s, "thz_session_cluster: a cluster's sum is not finite");
         cent.swap(next);
     }
     out->inertia = inertia;

@@ -134,24 +134,11 @@ int thz_session_echo_map(thz_session *s, int which, const thz_echo_cfg *cfg)
     if (int rc = session_cube(s, which, &c)) return rc;
     if (const char *why = echo_cfg_error(cfg, c.nt)) return fail(ctx, THZ_ERR_INVALID, std::string("thz_session_echo_map: ") + why);
     const size_t npix = c.nx * c.ny, K = (size_t)cfg->n_echoes;
-    // [index | offset | value: (K, npix) each | count: npix], four bytes an entry
-    s->echo_pix = s->echo_k = 0;
-    const size_t need = (3 * K + 1) * npix;
-    if (need > s->echo_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_echo) (void)hipFree(s->d_echo);
-        s->d_echo = nullptr;
-        s->echo_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_echo, need * sizeof(float)));
-        s->echo_cap = need;
-    }
-    if (int rc = thz_echo_map(ctx, npix, c.nt, c.d, cfg, reinterpret_cast<int32_t *>(s->d_echo), s->d_echo + K * npix,
-                              s->d_echo + 2 * K * npix, reinterpret_cast<int32_t *>(s->d_echo + 3 * K * npix)))
-        return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->echo_pix = npix;
-    s->echo_k = K;
-    return THZ_OK;
+    // [index | offset | value: (K, npix) each, rank-major | count: npix]
+    ResidentMaps &m = s->maps[kMapEcho];
+    if (int rc = maps_begin(ctx, &m, {{K * npix}, {K * npix}, {K * npix}, {npix}})) return rc;
+    if (int rc = thz_echo_map(ctx, npix, c.nt, c.d, cfg, m.ptr<int32_t>(0), m.ptr(1), m.ptr(2), m.ptr<int32_t>(3))) return rc;
+    return maps_commit(ctx, &m);
 }
 
 int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg)
@@ -160,28 +147,19 @@ int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg)
     thz_ctx *ctx = s->ctx;
     if (int rc = use_device(ctx)) return rc;
     if (!cfg) return fail(ctx, THZ_ERR_INVALID, "thz_session_layer_map: cfg is NULL");
-    if (!s->echo_pix) return fail(ctx, THZ_ERR_NOT_READY, "thz_session_layer_map: no echo map is resident (thz_session_echo_map)");
-    const size_t npix = s->echo_pix, K = s->echo_k;
+    // the resident echo maps: one count per pixel, K indices per pixel
+    const ResidentMaps &echo = s->maps[kMapEcho];
+    const size_t npix = echo.entries(3);
+    if (!npix) return fail(ctx, THZ_ERR_NOT_READY, "thz_session_layer_map: no echo map is resident (thz_session_echo_map)");
+    const size_t K = echo.entries(0) / npix;
     if (cfg->mode < 0 || cfg->mode > 1 || (cfg->mode == 0 && K < 2))
         return fail(ctx, THZ_ERR_INVALID, "thz_session_layer_map: mode is 0 (an echo map of two ranks or more) or 1");
     const size_t rows = cfg->mode == 0 ? K - 1 : 1;
     // [thickness | delay], (rows, npix) each
-    s->layer_pix = s->layer_rows = 0;
-    if (2 * rows * npix > s->layer_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_layer) (void)hipFree(s->d_layer);
-        s->d_layer = nullptr;
-        s->layer_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_layer, 2 * rows * npix * sizeof(float)));
-        s->layer_cap = 2 * rows * npix;
-    }
-    if (int rc = thz_layer_map(ctx, npix, (int)K, reinterpret_cast<const int32_t *>(s->d_echo), s->d_echo + K * npix, cfg,
-                               s->d_layer, s->d_layer + rows * npix))
-        return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->layer_pix = npix;
-    s->layer_rows = rows;
-    return THZ_OK;
+    ResidentMaps &m = s->maps[kMapLayer];
+    if (int rc = maps_begin(ctx, &m, {{rows * npix}, {rows * npix}})) return rc;
+    if (int rc = thz_layer_map(ctx, npix, (int)K, echo.ptr<const int32_t>(0), echo.ptr(1), cfg, m.ptr(0), m.ptr(1))) return rc;
+    return maps_commit(ctx, &m);
 }
 
 }  // extern "C"

@@ -68,32 +68,18 @@ int thz_session_optical_maps(thz_session *s, const float *ref_amp, const float *
                                               + std::to_string(s->nt_out / 2 + 1));
     if (const char *why = optical_cfg_error(cfg, nf)) return fail(ctx, THZ_ERR_INVALID, std::string("thz_session_optical_maps: ") + why);
     const size_t npix = s->nx_cur * s->ny_cur, nb = cfg->n_bands;
-    // the five images: [n | alpha | kappa] (n_bands, npix) each, then slope (npix); wraps apart
-    s->opt_pix = s->opt_bands = 0;
-    const size_t need = (3 * nb + 1) * npix;
-    if (need > s->opt_floats || npix > s->opt_wraps_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_opt) (void)hipFree(s->d_opt);
-        if (s->d_opt_wraps) (void)hipFree(s->d_opt_wraps);
-        s->d_opt = nullptr;
-        s->d_opt_wraps = nullptr;
-        s->opt_floats = s->opt_wraps_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_opt, (need ? need : 1) * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_opt_wraps, (npix ? npix : 1) * sizeof(int32_t)));
-        s->opt_floats = need;
-        s->opt_wraps_cap = npix;
-    }
+    // the five images: [n | alpha | kappa] (n_bands, npix) each, band-major — empty planes without bands — then wraps and
+    // slope (npix); the kernel stores them an element at a time
+    ResidentMaps &m = s->maps[kMapOptical];
+    if (int rc = maps_begin(ctx, &m, {{nb * npix}, {nb * npix}, {nb * npix}, {npix}, {npix}})) return rc;
     // the axis of the resident spectra, frequency[i] = i / (time[nt - 1] - time[0]) of the chain's final time axis
     std::vector<float> freq(nf);
     if (int rc = thz_host_frequency_axis(s->time_out.data(), s->nt_out, freq.data())) return rc;
     // the session's own pointers: thz_session_buffer would make the next recompute store every bin (session.hpp)
-    if (int rc = thz_optical_maps(ctx, npix, nf, s->d_amp, s->d_ph, ref_amp, ref_phase, freq.data(), cfg, d_thickness, s->d_opt,
-                                  s->d_opt + nb * npix, s->d_opt + 2 * nb * npix, s->d_opt_wraps, s->d_opt + 3 * nb * npix))
+    if (int rc = thz_optical_maps(ctx, npix, nf, s->d_amp, s->d_ph, ref_amp, ref_phase, freq.data(), cfg, d_thickness, m.ptr(0),
+                                  m.ptr(1), m.ptr(2), m.ptr<int32_t>(3), m.ptr(4)))
         return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->opt_pix = npix;
-    s->opt_bands = nb;
-    return THZ_OK;
+    return maps_commit(ctx, &m);
 }
 
 }  // extern "C"

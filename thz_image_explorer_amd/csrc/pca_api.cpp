@@ -170,27 +170,15 @@ int thz_session_pca_project(thz_session *s, int which, const thz_pca_cfg *cfg, c
     if (int rc = session_matrix(s, which, cfg, "principal components", &m)) return rc;
     if (bad_k(cfg)) return fail(ctx, THZ_ERR_INVALID, "thz_session_pca_project: 1 <= n_components <= min(count, THZ_PCA_MAX_COMPONENTS)");
     const size_t K = (size_t)cfg->n_components;
-    // [scores: (K, npix) | components: (K, L) | mean: L]
-    s->pca_pix = s->pca_k = s->pca_len = 0;
-    const size_t need = K * m.npix + (K + 1) * m.L;
-    if (need > s->pca_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_pca) (void)hipFree(s->d_pca);
-        s->d_pca = nullptr;
-        s->pca_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_pca, need * sizeof(float)));
-        s->pca_cap = need;
-    }
-    std::vector<float> tail((K + 1) * m.L, 0.0f);
+    // [scores: (K, npix), component-major | components: (K, L) | mean: L]
+    ResidentMaps &r = s->maps[kMapPca];
+    if (int rc = maps_begin(ctx, &r, {{K * m.npix}, {K * m.L}, {m.L}})) return rc;
+    std::vector<float> tail((K + 1) * m.L, 0.0f);  // the two planes behind the scores, in one copy
     std::memcpy(tail.data(), components, K * m.L * sizeof(float));
     if (mu) std::memcpy(tail.data() + K * m.L, mu, m.L * sizeof(float));
-    if (int rc = thz_memcpy_h2d(ctx, s->d_pca + K * m.npix, tail.data(), tail.size() * sizeof(float))) return rc;
-    if (int rc = thz_pca_scores(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, mu, components, (int)K, s->d_pca)) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->pca_pix = m.npix;
-    s->pca_k = K;
-    s->pca_len = m.L;
-    return THZ_OK;
+    if (int rc = thz_memcpy_h2d(ctx, r.ptr(1), tail.data(), tail.size() * sizeof(float))) return rc;
+    if (int rc = thz_pca_scores(ctx, m.npix, m.L, m.d, m.row_stride, m.col_step, mu, components, (int)K, r.ptr(0))) return rc;
+    return maps_commit(ctx, &r);
 }
 
 int thz_session_pca(thz_session *s, int which, const thz_pca_cfg *cfg, thz_pca_out *out)

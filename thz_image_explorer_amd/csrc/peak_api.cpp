@@ -43,12 +43,7 @@ int session_cube(thz_session *s, int which, SessionCube *out)
     out->d = static_cast<const float *>(session_buffer_ro(s, which));
     if (which == THZ_BUF_SPARSE) {  // the spike trains, on the grid and axis of the cube they were taken of
         if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: no spike trains are resident (thz_session_sparse_deconv)");
-        out->nx = s->sparse_nx;
-        out->ny = s->sparse_ny;
-        out->nt = s->sparse_nt;
-        out->dx = s->sparse_dx;
-        out->dy = s->sparse_dy;
-        out->dt_ps = s->sparse_dt_ps;
+        *out = s->sparse_cube;
         return THZ_OK;
     }
     if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: the cube is not available (no recompute has run)");
@@ -74,24 +69,11 @@ int thz_session_peak_map(thz_session *s, int which, int mode)
     SessionCube c;
     if (int rc = session_cube(s, which, &c)) return rc;
     const size_t npix = c.nx * c.ny;
-    s->peak_nx = s->peak_ny = 0;
-    if (npix > s->peak_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (void **p : {(void **)&s->d_peak_index, (void **)&s->d_peak_offset, (void **)&s->d_peak_value}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        s->peak_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_peak_index, npix * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_peak_offset, npix * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_peak_value, npix * sizeof(float)));
-        s->peak_cap = npix;
-    }
-    if (int rc = thz_peak_map(ctx, npix, c.nt, c.d, mode, s->d_peak_index, s->d_peak_offset, s->d_peak_value)) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->peak_nx = c.nx;
-    s->peak_ny = c.ny;
-    return THZ_OK;
+    // [index | offset | value], one entry per pixel of the mapped grid (the kernel stores them an element at a time)
+    ResidentMaps &m = s->maps[kMapPeak];
+    if (int rc = maps_begin(ctx, &m, {{npix}, {npix}, {npix}})) return rc;
+    if (int rc = thz_peak_map(ctx, npix, c.nt, c.d, mode, m.ptr<int32_t>(0), m.ptr(1), m.ptr(2))) return rc;
+    return maps_commit(ctx, &m);
 }
 
 int thz_session_estimate_tilt(thz_session *s, int which, int mode, float rel_threshold, thz_tilt_fit *out)
@@ -102,8 +84,9 @@ int thz_session_estimate_tilt(thz_session *s, int which, int mode, float rel_thr
     SessionCube c;
     if (int rc = session_cube(s, which, &c)) return rc;
     double m[10];
-    if (int rc = thz_arrival_plane_moments(s->ctx, c.nx, c.ny, c.dx, c.dy, c.dt_ps, s->d_peak_index, s->d_peak_offset,
-                                           s->d_peak_value, rel_threshold, m))
+    const ResidentMaps &peak = s->maps[kMapPeak];
+    if (int rc = thz_arrival_plane_moments(s->ctx, c.nx, c.ny, c.dx, c.dy, c.dt_ps, peak.ptr<int32_t>(0), peak.ptr(1), peak.ptr(2),
+                                           rel_threshold, m))
         return rc;
     return thz_host_arrival_plane_fit(m, out);
 }

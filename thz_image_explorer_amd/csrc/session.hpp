@@ -3,6 +3,7 @@
 #pragma once
 #include "ctx.hpp"
 
+#include <initializer_list>
 #include <vector>
 
 // One region of interest of a session (thz_session_set_rois) and its pixel list for the grid of the last recompute
@@ -14,6 +15,44 @@ struct SessionRoi {
     uint32_t total = 0;           // pixels of the WHOLE grid inside (= count unless the session is a group's slab)
     size_t for_rows = 0, for_cols = 0, for_scale = 0, for_x0 = 0, for_grid_rows = 0;  // what the list was built for
 };
+
+// A cube of a session with its grid, trace length, pixel pitch and the mean step of its time axis (session_cube)
+struct SessionCube {
+    const float *d = nullptr;
+    size_t nx = 0, ny = 0, nt = 0;
+    float dx = 1.0f, dy = 1.0f;
+    double dt_ps = 0.0;
+};
+
+// One family of per-pixel results that stays resident in a session and is read through thz_session_buffer /
+// thz_session_download: one grow-only device block of 4-byte words, cut into the planes of the family's last call.
+// A call is  maps_begin (the family is absent, the block holds the new layout)  ->  the launch on ptr(i)  ->
+// maps_commit (the stream has drained: resident).  Whatever fails in between leaves the family absent; a call refused
+// for its arguments never gets as far as maps_begin and leaves what was resident.  An upload voids every family.
+struct MapPlane {
+    size_t entries = 0;  // what thz_session_download bounds pix0 + npix against; 0: the plane is empty (NULL to a reader)
+    size_t per = 1;      // words per entry
+    size_t off = 0;      // where it starts in the block, in words: the planes follow one another (set by maps_begin)
+};
+struct ResidentMaps {
+    static constexpr int kMaxPlanes = 5;
+    float *d = nullptr;
+    size_t cap = 0;          // words allocated
+    bool resident = false;
+    MapPlane plane[kMaxPlanes];
+    // plane i of the layout of the last maps_begin, resident or not: what the call's launch writes
+    template <class T = float>
+    T *ptr(int i) const { return reinterpret_cast<T *>(d + plane[i].off); }
+    size_t entries(int i) const { return resident ? plane[i].entries : 0; }
+};
+// Marks the family absent, lays `planes` out one behind the other and makes sure of max(their words, min_words) words:
+// a block that is too small is freed — behind a synchronisation of the stream — and allocated anew (a failed
+// allocation leaves no block).
+int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> planes, size_t min_words = 0);
+// the call's closing synchronisation; the planes are resident when it has succeeded
+int maps_commit(thz_ctx *ctx, ResidentMaps *m);
+// A new family is a member here, its row in kMapIds (session_api.cpp) and its own *_api.cpp.
+enum MapFamily { kMapPeak, kMapOptical, kMapEcho, kMapLayer, kMapPca, kMapCluster, kMapSparse, kMapFamilies };
 
 struct thz_session {
     thz_ctx *ctx = nullptr;
@@ -55,43 +94,10 @@ struct thz_session {
     float *d_opacity = nullptr;                // voxel opacities of the final cube (thz_session_voxels)
     size_t opacity_floats = 0;
     int32_t *d_ins = nullptr;
-    // arrival-time maps of the last thz_session_peak_map (peak_api.cpp): one entry per pixel of the grid it mapped
-    int32_t *d_peak_index = nullptr;
-    float *d_peak_offset = nullptr, *d_peak_value = nullptr;
-    size_t peak_cap = 0;                       // pixels allocated
-    size_t peak_nx = 0, peak_ny = 0;           // the mapped grid; 0 x 0: the maps are absent
-    // optical-property maps of the last thz_session_optical_maps (optical_api.cpp):
-    // d_opt = [n | alpha | kappa: (opt_bands, opt_pix) each | slope: opt_pix]
-    float *d_opt = nullptr;
-    int32_t *d_opt_wraps = nullptr;
-    size_t opt_floats = 0, opt_wraps_cap = 0;  // allocated
-    size_t opt_pix = 0, opt_bands = 0;         // pixels and bands of the last call; 0 pixels: the maps are absent
-    // echo maps of the last thz_session_echo_map (echo_api.cpp), four bytes an entry:
-    // d_echo = [index | offset | value: (echo_k, echo_pix) each, rank-major | count: echo_pix]
-    float *d_echo = nullptr;
-    size_t echo_cap = 0;                       // entries allocated
-    size_t echo_pix = 0, echo_k = 0;           // pixels and ranks of the last call; 0 pixels: the maps are absent
-    // ... and what the last thz_session_layer_map made of them: d_layer = [thickness | delay: (layer_rows, layer_pix) each]
-    float *d_layer = nullptr;
-    size_t layer_cap = 0;
-    size_t layer_pix = 0, layer_rows = 0;
-    // principal components of the last thz_session_pca / _pca_project (pca_api.cpp):
-    // d_pca = [scores: (pca_k, pca_pix), component-major | components: (pca_k, pca_len) | mean: pca_len]
-    float *d_pca = nullptr;
-    size_t pca_cap = 0;                        // floats allocated
-    size_t pca_pix = 0, pca_k = 0, pca_len = 0;  // pixels, components and columns of the last call; 0 pixels: absent
-    // k-means of the last thz_session_cluster / _cluster_step (cluster_api.cpp):
-    // d_cluster = [labels: cluster_pix int32 | dist2: cluster_pix f32 | centroids: (cluster_k, cluster_len) f32]
-    float *d_cluster = nullptr;
-    size_t cluster_cap = 0;                                  // 4-byte words allocated
-    size_t cluster_pix = 0, cluster_k = 0, cluster_len = 0;  // of the last step; 0 pixels: absent
-    // spike trains of the last thz_session_sparse_deconv (sparse_api.cpp), four bytes an entry:
-    // d_sparse = [x: (pixels, sparse_nt) | residual: pixels f32 | non-zeros: pixels int32]
-    float *d_sparse = nullptr;
-    size_t sparse_cap = 0;                                 // entries allocated
-    size_t sparse_nx = 0, sparse_ny = 0, sparse_nt = 0;    // grid and trace length of the cube they were taken of; 0: absent
-    float sparse_dx = 1.0f, sparse_dy = 1.0f;              // ... its pixel pitch
-    double sparse_dt_ps = 0.0;                             // ... and the mean step of its time axis
+    // the analysis maps of the last call of each family (ResidentMaps above): the planes are those of the family's
+    // THZ_BUF_* ids, in their order (kMapIds in session_api.cpp)
+    ResidentMaps maps[kMapFamilies];
+    SessionCube sparse_cube;     // kMapSparse: the spike trains as a cube, on the grid, pitch and time step of the cube they were taken of
     float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     size_t msum_floats = 0;
@@ -194,12 +200,6 @@ void session_roi_free(thz_session *s);
 // peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA, or THZ_BUF_SPARSE: the spike trains, on the grid
 // and time axis of the cube they were taken of) with its grid, trace length and the mean step of its time axis;
 // THZ_ERR_NOT_READY when it is absent
-struct SessionCube {
-    const float *d = nullptr;
-    size_t nx = 0, ny = 0, nt = 0;
-    float dx = 1.0f, dy = 1.0f;
-    double dt_ps = 0.0;
-};
 int session_cube(thz_session *s, int which, SessionCube *out);
 // the ifft stage's avg_data (avg_in_fourier_space; needs the means): host-side, after session_means
 int session_avg_data(thz_session *s, const thz_chain_cfg *cfg);

@@ -100,11 +100,10 @@ void thz_session_destroy(thz_session *s)
     for (void *p : {(void *)s->d_raw, (void *)s->d_fft, (void *)s->d_amp, (void *)s->d_ph, (void *)s->d_data,
                     (void *)s->d_img, (void *)s->d_avg, (void *)s->d_vec, (void *)s->d_tilt, (void *)s->d_ins,
                     (void *)s->d_opacity, (void *)s->d_deconv, (void *)s->d_deconv_img, (void *)s->d_scaled,
-                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out,
-                    (void *)s->d_peak_index, (void *)s->d_peak_offset, (void *)s->d_peak_value, (void *)s->d_opt,
-                    (void *)s->d_opt_wraps, (void *)s->d_echo, (void *)s->d_layer, (void *)s->d_pca,
-                    (void *)s->d_cluster, (void *)s->d_sparse})
+                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out})
         if (p) (void)hipFree(p);
+    for (ResidentMaps &m : s->maps)
+        if (m.d) (void)hipFree(m.d);
     if (s->h_vec) (void)hipHostFree(s->h_vec);
     session_roi_free(s);
     delete s;
@@ -121,12 +120,7 @@ int thz_session_upload(thz_session *s, const float *cube, int subtract_bias)
     s->have_outputs = false; s->have_means = false; s->deconv_current = false;
     s->scale = 1; s->nx_cur = s->nx; s->ny_cur = s->ny; s->dx_cur = s->dx; s->dy_cur = s->dy;
     ++s->src_gen;  // new source traces: the regions' kept sums of them are void
-    s->peak_nx = s->peak_ny = 0;  // ... and so are the arrival-time maps
-    s->opt_pix = s->opt_bands = 0;  // ... and the optical-property maps
-    s->echo_pix = s->echo_k = s->layer_pix = s->layer_rows = 0;  // ... and the echo and layer maps
-    s->pca_pix = s->pca_k = s->pca_len = 0;  // ... and the principal components
-    s->cluster_pix = s->cluster_k = s->cluster_len = 0;  // ... and the segmentation
-    s->sparse_nx = s->sparse_ny = s->sparse_nt = 0;  // ... and the spike trains
+    for (ResidentMaps &m : s->maps) m.resident = false;  // ... and so is every family of analysis maps
     if (cube) HIP_TRY(ctx, hipMemcpyAsync(s->d_raw, cube, npix * s->nt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     launch_intensity(ctx->stream, npix, (int)s->nt, s->d_raw, s->d_img, subtract_bias ? 1 : 0);
     if (int rc = check_launch(ctx)) return rc;
@@ -708,57 +702,70 @@ void *thz_session_buffer(thz_session *s, int which)
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------
+// The resident analysis maps (session.hpp, ResidentMaps): the one place where their blocks are
+// allocated, and the one table from a THZ_BUF_* id to a family's plane.
+// ---------------------------------------------------------------------------------------------
+int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> planes, size_t min_words)
+{
+    m->resident = false;
+    size_t need = 0;
+    int i = 0;
+    for (MapPlane p : planes) {
+        p.off = need;
+        need += p.entries * p.per;
+        m->plane[i++] = p;
+    }
+    for (; i < ResidentMaps::kMaxPlanes; ++i) m->plane[i] = MapPlane{};
+    need = std::max(need, min_words);
+    if (need > m->cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (m->d) (void)hipFree(m->d);
+        m->d = nullptr;
+        m->cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&m->d, need * sizeof(float)));
+        m->cap = need;
+    }
+    return THZ_OK;
+}
+
+int maps_commit(thz_ctx *ctx, ResidentMaps *m)
+{
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    m->resident = true;
+    return THZ_OK;
+}
+
+namespace {
+
+// A family's ids are contiguous and in the order of its planes: the first id and how many.  The arrival-time, echo and
+// spike-train maps belong to whichever cube was mapped last, the raw one included; the optical-property maps to the
+// spectra of the recompute they were taken of; the layer maps to the echo maps they were made of; the principal
+// components and the segmentation to whichever matrix they were taken of.
+const struct { int first, planes; } kMapIds[kMapFamilies] = {
+    {THZ_BUF_PEAK_INDEX, 3}, {THZ_BUF_OPT_N, 5},          {THZ_BUF_ECHO_INDEX, 4}, {THZ_BUF_LAYER_THICKNESS, 2},
+    {THZ_BUF_PCA_SCORES, 3}, {THZ_BUF_CLUSTER_LABELS, 3}, {THZ_BUF_SPARSE, 3}};
+
+// the plane `which` names (and its family), resident or not; null: `which` is no analysis map
+const MapPlane *map_plane(const thz_session *s, int which, const ResidentMaps **family = nullptr)
+{
+    for (int f = 0; f < kMapFamilies; ++f)
+        if (which >= kMapIds[f].first && which < kMapIds[f].first + kMapIds[f].planes) {
+            if (family) *family = &s->maps[f];
+            return &s->maps[f].plane[which - kMapIds[f].first];
+        }
+    return nullptr;
+}
+
+}  // namespace
+
 // thz_session_buffer for the library's own readers (downloads, a group's gathers)
 const void *session_buffer_ro(thz_session *s, int which)
 {
     if (!s) return nullptr;
     const size_t nf = s->nf_out;
-    // the arrival-time maps belong to whichever cube was mapped last, the raw one included
-    if (which == THZ_BUF_PEAK_INDEX || which == THZ_BUF_PEAK_OFFSET || which == THZ_BUF_PEAK_VALUE) {
-        if (!s->peak_nx || !s->peak_ny) return nullptr;
-        return which == THZ_BUF_PEAK_INDEX ? (const void *)s->d_peak_index
-               : which == THZ_BUF_PEAK_OFFSET ? (const void *)s->d_peak_offset : (const void *)s->d_peak_value;
-    }
-    // the optical-property maps belong to the spectra of the recompute they were taken of
-    if (which >= THZ_BUF_OPT_N && which <= THZ_BUF_OPT_SLOPE) {
-        if (!s->opt_pix) return nullptr;
-        const size_t plane = s->opt_bands * s->opt_pix;
-        switch (which) {
-        case THZ_BUF_OPT_N: return s->opt_bands ? s->d_opt : nullptr;
-        case THZ_BUF_OPT_ALPHA: return s->opt_bands ? s->d_opt + plane : nullptr;
-        case THZ_BUF_OPT_KAPPA: return s->opt_bands ? s->d_opt + 2 * plane : nullptr;
-        case THZ_BUF_OPT_WRAPS: return s->d_opt_wraps;
-        default: return s->d_opt + 3 * plane;
-        }
-    }
-    // the echo maps belong to whichever cube was mapped last, like the arrival-time maps; the layer maps to the echo maps
-    // they were made of
-    if (which >= THZ_BUF_ECHO_INDEX && which <= THZ_BUF_ECHO_COUNT) {
-        if (!s->echo_pix) return nullptr;
-        return s->d_echo + (size_t)(which - THZ_BUF_ECHO_INDEX) * s->echo_k * s->echo_pix;
-    }
-    if (which == THZ_BUF_LAYER_THICKNESS || which == THZ_BUF_LAYER_DELAY) {
-        if (!s->layer_pix) return nullptr;
-        return which == THZ_BUF_LAYER_THICKNESS ? s->d_layer : s->d_layer + s->layer_rows * s->layer_pix;
-    }
-    // the principal components belong to whichever matrix they were taken of
-    if (which >= THZ_BUF_PCA_SCORES && which <= THZ_BUF_PCA_MEAN) {
-        if (!s->pca_pix) return nullptr;
-        return which == THZ_BUF_PCA_SCORES ? s->d_pca
-               : which == THZ_BUF_PCA_COMPONENTS ? s->d_pca + s->pca_k * s->pca_pix
-                                                 : s->d_pca + s->pca_k * s->pca_pix + s->pca_k * s->pca_len;
-    }
-    // ... and so does the segmentation
-    if (which >= THZ_BUF_CLUSTER_LABELS && which <= THZ_BUF_CLUSTER_CENTROIDS) {
-        if (!s->cluster_pix) return nullptr;
-        return s->d_cluster + (size_t)(which - THZ_BUF_CLUSTER_LABELS) * s->cluster_pix;
-    }
-    // the spike trains belong to whichever cube was deconvolved last, the raw one included
-    if (which >= THZ_BUF_SPARSE && which <= THZ_BUF_SPARSE_NNZ) {
-        const size_t pix = s->sparse_nx * s->sparse_ny;
-        if (!pix || !s->sparse_nt) return nullptr;
-        return which == THZ_BUF_SPARSE ? s->d_sparse : s->d_sparse + pix * (s->sparse_nt + (size_t)(which - THZ_BUF_SPARSE_RESID));
-    }
+    const ResidentMaps *m = nullptr;
+    if (const MapPlane *p = map_plane(s, which, &m)) return m->resident && p->entries ? m->d + p->off : nullptr;
     // Before the first recompute (and between an upload and the next recompute) the output buffers hold
     // nothing a caller may read — and after a scaled recompute they are sized for the smaller grid while
     // the session's grid is the raw one again: absent (NULL / THZ_ERR_NOT_READY) until a recompute has run.
@@ -787,42 +794,27 @@ int thz_session_download(thz_session *s, int which, size_t pix0, size_t npix, vo
     thz_ctx *ctx = s->ctx;
     const float *base = static_cast<const float *>(session_buffer_ro(s, which));
     if (!base) return fail(ctx, THZ_ERR_NOT_READY, "thz_session_download: buffer not available");
-    size_t per = 0;  // floats per pixel
-    // per-pixel outputs were allocated for out_pix pixels by the recompute that filled them; the image has
-    // nx * ny entries (allocated once) of which the current grid's are valid
-    const bool peak = which == THZ_BUF_PEAK_INDEX || which == THZ_BUF_PEAK_OFFSET || which == THZ_BUF_PEAK_VALUE;
-    const bool opt_band = which == THZ_BUF_OPT_N || which == THZ_BUF_OPT_ALPHA || which == THZ_BUF_OPT_KAPPA;
-    const size_t total_pix = which == THZ_BUF_RAW ? s->nx * s->ny
-                             : peak ? s->peak_nx * s->peak_ny
-                             : opt_band ? s->opt_bands * s->opt_pix  // the flattened (band, pixel) array
-                             : (which == THZ_BUF_OPT_WRAPS || which == THZ_BUF_OPT_SLOPE) ? s->opt_pix
-                             : (which >= THZ_BUF_ECHO_INDEX && which <= THZ_BUF_ECHO_VALUE) ? s->echo_k * s->echo_pix  // (rank, pixel)
-                             : which == THZ_BUF_ECHO_COUNT ? s->echo_pix
-                             : (which == THZ_BUF_LAYER_THICKNESS || which == THZ_BUF_LAYER_DELAY) ? s->layer_rows * s->layer_pix
-                             : which == THZ_BUF_PCA_SCORES ? s->pca_k * s->pca_pix  // the flattened (component, pixel) array
-                             : which == THZ_BUF_PCA_COMPONENTS ? s->pca_k * s->pca_len
-                             : which == THZ_BUF_PCA_MEAN ? s->pca_len
-                             : (which == THZ_BUF_CLUSTER_LABELS || which == THZ_BUF_CLUSTER_DIST) ? s->cluster_pix
-                             : which == THZ_BUF_CLUSTER_CENTROIDS ? s->cluster_k * s->cluster_len
-                             : (which >= THZ_BUF_SPARSE && which <= THZ_BUF_SPARSE_NNZ) ? s->sparse_nx * s->sparse_ny
-                             : which == THZ_BUF_IMG ? s->nx_cur * s->ny_cur
-                                                    : (s->out_pix < s->nx_cur * s->ny_cur ? s->out_pix : s->nx_cur * s->ny_cur);
-    switch (which) {
-    case THZ_BUF_RAW: per = s->nt; break;
-    case THZ_BUF_FFT: per = 2 * s->nf_out; break;
-    case THZ_BUF_AMPLITUDES: case THZ_BUF_PHASES: per = s->nf_out; break;
-    case THZ_BUF_DATA: case THZ_BUF_OPACITY: per = s->nt_out; break;
-    case THZ_BUF_IMG: case THZ_BUF_PEAK_INDEX: case THZ_BUF_PEAK_OFFSET: case THZ_BUF_PEAK_VALUE: per = 1; break;  // 4 bytes each
-    case THZ_BUF_OPT_N: case THZ_BUF_OPT_ALPHA: case THZ_BUF_OPT_KAPPA: case THZ_BUF_OPT_WRAPS: case THZ_BUF_OPT_SLOPE: per = 1; break;
-    case THZ_BUF_ECHO_INDEX: case THZ_BUF_ECHO_OFFSET: case THZ_BUF_ECHO_VALUE: case THZ_BUF_ECHO_COUNT:
-    case THZ_BUF_LAYER_THICKNESS: case THZ_BUF_LAYER_DELAY: per = 1; break;
-    case THZ_BUF_PCA_SCORES: case THZ_BUF_PCA_COMPONENTS: case THZ_BUF_PCA_MEAN: per = 1; break;
-    case THZ_BUF_CLUSTER_LABELS: case THZ_BUF_CLUSTER_DIST: case THZ_BUF_CLUSTER_CENTROIDS: per = 1; break;
-    case THZ_BUF_SPARSE: per = s->sparse_nt; break;
-    case THZ_BUF_SPARSE_RESID: case THZ_BUF_SPARSE_NNZ: per = 1; break;
-    case THZ_BUF_AVG_FFT: return thz_memcpy_d2h(ctx, dst, base, 2 * s->nf_out * sizeof(float));
-    case THZ_BUF_AVG_AMPLITUDES: case THZ_BUF_AVG_PHASES: return thz_memcpy_d2h(ctx, dst, base, s->nf_out * sizeof(float));
-    default: return THZ_ERR_INVALID;
+    size_t total_pix = 0, per = 0;  // pixels; floats per pixel
+    if (const MapPlane *p = map_plane(s, which)) {
+        // an analysis map: the entries of its plane (a flattened (band | rank | component, pixel) array counts all of them)
+        total_pix = p->entries;
+        per = p->per;
+    } else {
+        // per-pixel outputs were allocated for out_pix pixels by the recompute that filled them; the image has
+        // nx * ny entries (allocated once) of which the current grid's are valid
+        total_pix = which == THZ_BUF_RAW ? s->nx * s->ny
+                    : which == THZ_BUF_IMG ? s->nx_cur * s->ny_cur
+                                           : (s->out_pix < s->nx_cur * s->ny_cur ? s->out_pix : s->nx_cur * s->ny_cur);
+        switch (which) {
+        case THZ_BUF_RAW: per = s->nt; break;
+        case THZ_BUF_FFT: per = 2 * s->nf_out; break;
+        case THZ_BUF_AMPLITUDES: case THZ_BUF_PHASES: per = s->nf_out; break;
+        case THZ_BUF_DATA: case THZ_BUF_OPACITY: per = s->nt_out; break;
+        case THZ_BUF_IMG: per = 1; break;
+        case THZ_BUF_AVG_FFT: return thz_memcpy_d2h(ctx, dst, base, 2 * s->nf_out * sizeof(float));
+        case THZ_BUF_AVG_AMPLITUDES: case THZ_BUF_AVG_PHASES: return thz_memcpy_d2h(ctx, dst, base, s->nf_out * sizeof(float));
+        default: return THZ_ERR_INVALID;
+        }
     }
     if (pix0 > total_pix || npix > total_pix - pix0) return fail(ctx, THZ_ERR_INVALID, "thz_session_download: pixel range out of bounds");
     return thz_memcpy_d2h(ctx, dst, base + pix0 * per, npix * per * sizeof(float));

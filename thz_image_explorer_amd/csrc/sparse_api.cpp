@@ -43,28 +43,14 @@ int thz_session_sparse_deconv(thz_session *s, int which, const float *taps, cons
     if (int rc = session_cube(s, which, &c)) return rc;
     if (const char *why = sparse_cfg_error(cfg, c.nt, taps)) return fail(ctx, THZ_ERR_INVALID, std::string("thz_session_sparse_deconv: ") + why);
     const size_t npix = c.nx * c.ny;
-    // [x: (npix, nt) | resid: npix | nnz: npix], four bytes an entry
-    s->sparse_nx = s->sparse_ny = s->sparse_nt = 0;
-    const size_t need = npix * (c.nt + 2);
-    if (need > s->sparse_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->d_sparse) (void)hipFree(s->d_sparse);
-        s->d_sparse = nullptr;
-        s->sparse_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->d_sparse, need * sizeof(float)));
-        s->sparse_cap = need;
-    }
-    if (int rc = thz_sparse_deconv(ctx, npix, c.nt, c.d, taps, cfg, s->d_sparse, s->d_sparse + npix * c.nt,
-                                   reinterpret_cast<int32_t *>(s->d_sparse + npix * (c.nt + 1))))
-        return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    s->sparse_nx = c.nx;
-    s->sparse_ny = c.ny;
-    s->sparse_nt = c.nt;
-    s->sparse_dx = c.dx;
-    s->sparse_dy = c.dy;
-    s->sparse_dt_ps = c.dt_ps;
-    return THZ_OK;
+    // [x: (npix, nt) | resid: npix | nnz: npix]
+    ResidentMaps &m = s->maps[kMapSparse];
+    if (int rc = maps_begin(ctx, &m, {{npix, c.nt}, {npix}, {npix}})) return rc;
+    if (int rc = thz_sparse_deconv(ctx, npix, c.nt, c.d, taps, cfg, m.ptr(0), m.ptr(1), m.ptr<int32_t>(2))) return rc;
+    // the spike trains as a cube for the per-trace maps: on the grid, pitch and time step of the cube they were taken of
+    s->sparse_cube = c;
+    s->sparse_cube.d = m.ptr(0);
+    return maps_commit(ctx, &m);
 }
 
 }  // extern "C"
