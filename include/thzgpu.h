@@ -826,7 +826,13 @@ int thz_session_recompute(thz_session *s, const thz_chain_cfg *cfg);
  * intermediate.  Positions 6 and 7 re-run only C2R -> Time Band Pass -> image on the resident spectrum
  * (a third of the full chain's traffic) — provided the last full recompute used the same settings in
  * front of position 6, else they fall back to the full chain.  Position 8 is thz_session_deconvolve's;
- * here it is a no-op. */
+ * here it is a no-op.
+ * The unwrapped phases are those of the transform in front of the Frequency Band Pass and its plugins: they
+ * depend on the source traces, the scale factor, the tilt and the multipliers in front of the transform
+ * (tilt taper, Time Band Pass, fft window) alone.  A full recompute that changes none of these — a drag on
+ * the Frequency Band Pass, a plugin, the Time Band Pass (after) — leaves THZ_BUF_PHASES and the phases'
+ * pixel sums as they are instead of computing the same values again (nt = 4096, a band that ends at or
+ * below bin 1152; every other recompute computes them).  The outputs are the same either way. */
 int thz_session_recompute_from(thz_session *s, const thz_chain_cfg *cfg, int start_stage);
 /* Further Frequency-domain plugins of the chain (FilterDomain::Frequency, behind "Frequency Band Pass"),
  * as per-bin multipliers for the chain's nf bins (host vectors, copied; NULL removes one): a real one —
@@ -888,7 +894,11 @@ int thz_session_time_out(const thz_session *s, float *time /* nt_out */);
  * storing them again.  A caller may write through the pointer until the NEXT recompute: every call of this
  * function for one of the two makes that recompute store every bin.  Writing through a pointer obtained
  * earlier, after a later recompute, is outside the contract — bins outside the band would keep what was
- * written.  (The same holds for the sessions of a group, thz_group_session_member.) */
+ * written.  (The same holds for the sessions of a group, thz_group_session_member.)
+ * THZ_BUF_PHASES likewise: the session is its only writer and leaves the phases in place while nothing
+ * they depend on changes (thz_session_recompute_from); every call of this function for THZ_BUF_PHASES or
+ * for THZ_BUF_RAW makes the next recompute compute and store them all.  A raw cube written through a held
+ * pointer is followed by thz_session_upload(s, NULL, ...) as before. */
 void *thz_session_buffer(thz_session *s, int which);
 /* copies pixels [pix0, pix0+npix) of a per-pixel buffer (or the whole vector for
  * the AVG_* ones, pix0 = 0, npix = 1) to the host: the selected-pixel trace, a

@@ -471,7 +471,7 @@ int thz_pipeline_ex(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io)
 // (fft_f.hpp, "band pruning"); one that writes every bin computes every bin.
 int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi, KeepRange *keep)
 {
-    if (keep) keep->honoured = false;
+    if (keep) keep->honoured = keep->phases_honoured = false;
     if (int rc = need_plan(ctx)) return rc;
     int keep_lo4 = 0, keep_n = -1;  // every bin
     if (keep && !keep->all && keep->hi >= keep->lo && keep->hi <= (size_t)ctx->plan_d.nf && pipeline_keeps_range(ctx->plan_d)) {
@@ -507,16 +507,21 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
         StageTimer t(ctx, THZ_STAGE_PIPELINE);
         launch_pipeline(ctx->stream, ctx->plan_d, npix, io->d_raw, io->d_pre_win, io->d_fd_mask, io->d_post_win,
                         reinterpret_cast<c32 *>(io->d_fft), io->d_amp, io->d_phase, io->d_data_out, io->d_img,
-                        reinterpret_cast<const c32 *>(io->d_fd_cmask), d_partial, band_lo4, band_n, keep_lo4, keep_n);
+                        reinterpret_cast<const c32 *>(io->d_fd_cmask), d_partial, band_lo4, band_n, keep_lo4, keep_n,
+                        keep && keep->phases && keep_n >= 0);
         if (int rc = check_launch(ctx)) return rc;
     }
+    const bool phases_kept = pipeline_kept_phases();
     if (keep) keep->honoured = pipeline_keeps_range(ctx->plan_d);  // (told "every bin" it obeyed that)
+    if (keep) keep->phases_honoured = phases_kept;
     if (!io->d_sums) return THZ_OK;
     if (d_partial) {
         StageTimer t(ctx, THZ_STAGE_MEAN);
-        launch_sum_rows_f64(ctx->stream, d_partial, sum_rows, 2 * nf, io->d_sums);
+        // kept phases: rows of nf amplitude sums; the second half of d_sums is the caller's
+        launch_sum_rows_f64(ctx->stream, d_partial, sum_rows, phases_kept ? nf : 2 * nf, io->d_sums);
         return check_launch(ctx);
     }
+    // (kept phases: d_phase holds them, the pass below sums what is resident)
     if (int rc = thz_pixel_sum(ctx, npix, nf, 1, io->d_amp, io->d_sums)) return rc;
     return thz_pixel_sum(ctx, npix, nf, 1, io->d_phase, io->d_sums + nf);
 }

@@ -227,10 +227,16 @@ using namespace thz_api;
 // what they hold (the session): [lo, hi), widened to multiples of 4; the launch may leave every other bin of the two
 // arrays untouched.  all = true (the default): every bin.  `honoured` comes back true when the launch that ran is one
 // that obeys such a range (the F family), false when it wrote everything whatever it was told, or failed.
+// phases = true: the caller also knows d_phase to hold the phases this launch would write — those of FFT(pre x), which
+// no multiplier behind the transform touches — and, if it asks for sums, has the phase sums itself.  phases_honoured
+// comes back true when the launch left d_phase alone (fft_f.hpp, "kept phases"): d_sums then holds the amplitude sums
+// in its first nf floats and its second nf floats were not written.  false: the launch computed phases as ever.
 struct KeepRange {
     size_t lo = 0, hi = 0;
     bool all = true;
     bool honoured = false;
+    bool phases = false;
+    bool phases_honoured = false;
 };
 // api.cpp: thz_pipeline_ex with the real multiplier's non-zero range [band_lo, band_hi) known (0, 0: unknown)
 int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_t band_lo, size_t band_hi, KeepRange *keep = nullptr);

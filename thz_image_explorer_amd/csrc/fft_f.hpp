@@ -262,10 +262,12 @@ enum : int {
     kCfgLow = 64,      // with kCfgKeep: the multiplier is zero from bin N/2 + M1 on and the keep range ends there at the
                        // latest — f_inverse_input leaves out the half-terms that are products with those zeros ("band
                        // pruning" below)
-    kCfgBand = 16      // with kCfgCMask: the staged multiplier table covers only the bins FArgs::band_lo4 .. + band_n — where
+    kCfgBand = 16,     // with kCfgCMask: the staged multiplier table covers only the bins FArgs::band_lo4 .. + band_n — where
                        // the real band pass is not zero — between two quads of zeros that every other bin's index is clamped
                        // to.  Half the table at the default 0.2-5 THz: what lets the nt = 4096 chain with the complex
                        // multiplier AND the in-launch sums keep eight waves per block (round 3).
+    kCfgKeepPhases = 128  // with kCfgLow: the launch leaves the phases alone — ph_out is never touched, and the block's sum
+                          // rows are nf floats long and hold the amplitude sums only ("kept phases" below)
 };
 
 // ------------------------------------------------------------------- the plan
@@ -774,6 +776,13 @@ __device__ __forceinline__ void load_f4(const float *p, float &a, float &b, floa
 // differ only where that value is itself a zero (so a multiplier of -0 outside the band is as good as +0).
 // band_n == 0: nothing is known, nothing is pruned.  (The spectrum epilogue computes every group: skipping the
 // multiplier, products and square roots of the groups wholly outside the band was tried and measured no gain.)
+// Kept phases.  The unwrapped phases are those of X = FFT(pre x), taken in front of the multiplier: they depend on the
+// source traces and the pre-transform multiplier alone.  A caller that knows ph_out to hold them already — the session,
+// from one recompute to the next while neither changes — says so to launch_pipeline, and the kCfgLow builds of the
+// nt = 4096 plan then run their kCfgKeepPhases form: the spectrum epilogue without the arctangents, the unwrap, its
+// wave scan and carries, the phase store and the phase half of the sums (FSums<...>::group<false>).  ph_out is not
+// read either.  The block's row of sum_partial is then nf floats long, the amplitude sums; the caller adds the rows
+// as such and supplies the phase sums it kept.  Every other output is the bits of the launch that computes phases.
 constexpr int kFKeepAll = 1 << 30;
 
 // A window of an output row whose stores carry a per-lane predicate at no cost in control flow or registers: the
@@ -991,6 +1000,8 @@ struct FSums {
     unsigned early_t;
 #endif
     // issues the visit's LDS reads (ticket + the group's accumulators); group() consumes them
+    // PH = false (here, in group() and in finish()): amplitudes only — the phase half of the area is never touched
+    template <bool PH = true>
     __device__ __forceinline__ void begin(int g, int lane)
     {
 #ifndef THZ_EMU
@@ -1000,13 +1011,14 @@ struct FSums {
         early_t = __hip_atomic_load(tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         asm volatile("" ::: "memory");
         early_a = *reinterpret_cast<const f4e *>(sa);
-        early_p = *reinterpret_cast<const f4e *>(sa + N);
+        if constexpr (PH) early_p = *reinterpret_cast<const f4e *>(sa + N);
         asm volatile("" ::: "memory");
 #else
         (void)g; (void)lane;
 #endif
     }
     // adds this wave's group-g values of its current trace to the block's sums, in ticket order
+    template <bool PH = true>
     __device__ __forceinline__ void group(int g, const float (&a)[4], const float (&y)[4], int lane)
     {
         unsigned *tick = reinterpret_cast<unsigned *>(area + 2 * N) + g;
@@ -1021,9 +1033,12 @@ struct FSums {
                 break;
             }
         }
-        const float4 va = *reinterpret_cast<const float4 *>(sa), vp = *reinterpret_cast<const float4 *>(sp);
+        const float4 va = *reinterpret_cast<const float4 *>(sa);
         *reinterpret_cast<float4 *>(sa) = make_float4(va.x + a[0], va.y + a[1], va.z + a[2], va.w + a[3]);
-        *reinterpret_cast<float4 *>(sp) = make_float4(vp.x + y[0], vp.y + y[1], vp.z + y[2], vp.w + y[3]);
+        if constexpr (PH) {
+            const float4 vp = *reinterpret_cast<const float4 *>(sp);
+            *reinterpret_cast<float4 *>(sp) = make_float4(vp.x + y[0], vp.y + y[1], vp.z + y[2], vp.w + y[3]);
+        }
         wave_sync();  // every lane's update is issued before lane 0 hands the ticket on
         if (lane == 0) lds_flag_store(tick, mine + 1u);
 #else
@@ -1037,14 +1052,15 @@ struct FSums {
         typedef float f4v __attribute__((ext_vector_type(4)));
         // the first attempt's reads were issued by begin(), in front of the group's arctangents and unwrap: their
         // latency is behind the wave when it gets here (a stale ticket only costs the re-read below)
-        f4v va = early_a, vp = early_p;
+        f4v va = early_a, vp = early_a;
+        if constexpr (PH) vp = early_p;
         unsigned t = early_t;
         for (;;) {
             if (THZ_UNIFORM((int)t) == (int)mine) break;
             t = __hip_atomic_load(tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             asm volatile("" ::: "memory");
             va = *reinterpret_cast<const f4v *>(sa);  // (plain loads: a volatile access through the generic pointer
-            vp = *reinterpret_cast<const f4v *>(sp);  //  loses the LDS address space and becomes a flat load)
+            if constexpr (PH) vp = *reinterpret_cast<const f4v *>(sp);  //  loses the LDS address space and becomes a flat load)
             asm volatile("" ::: "memory");
             if (THZ_UNIFORM((int)t) == (int)mine) break;
             spin_pause();
@@ -1054,7 +1070,7 @@ struct FSums {
             }
         }
         *reinterpret_cast<float4 *>(sa) = make_float4(va.x + a[0], va.y + a[1], va.z + a[2], va.w + a[3]);
-        *reinterpret_cast<float4 *>(sp) = make_float4(vp.x + y[0], vp.y + y[1], vp.z + y[2], vp.w + y[3]);
+        if constexpr (PH) *reinterpret_cast<float4 *>(sp) = make_float4(vp.x + y[0], vp.y + y[1], vp.z + y[2], vp.w + y[3]);
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) __hip_atomic_store(tick, mine + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1062,12 +1078,14 @@ struct FSums {
 #endif
     }
     // after the trace loop (and a block barrier): bin N across the waves, then the block's row of sum_partial
+    // (PH = false: a row of nf amplitude sums)
+    template <bool PH = true>
     __device__ __forceinline__ void finish(float *row, int nf, int lane)
     {
         float *scratch = area + 2 * N + kTickets;
         if (lane == 0) {
             scratch[wib] = nyq_a;
-            scratch[16 + wib] = nyq_p;
+            if constexpr (PH) scratch[16 + wib] = nyq_p;
             if (give_up) area[0] = __builtin_nanf("");
         }
         block_lds_barrier();  // all waves are through their last group and have left their bin-N sums
@@ -1075,14 +1093,14 @@ struct FSums {
             float a = 0.0f, ph = 0.0f;
             for (int w = 0; w < wpb; ++w) {
                 a += scratch[w];
-                ph += scratch[16 + w];
+                if constexpr (PH) ph += scratch[16 + w];
             }
             row[nf - 1] = a;
-            row[2 * nf - 1] = ph;
+            if constexpr (PH) row[2 * nf - 1] = ph;
         }
         for (int i = wib * kWave + lane; i < N; i += wpb * kWave) {
             row[i] = area[i];
-            row[nf + i] = area[N + i];
+            if constexpr (PH) row[nf + i] = area[N + i];
         }
     }
 };
@@ -1094,8 +1112,12 @@ struct FSums {
 // KEEP (fused chain): amplitudes and bin N are stored inside the keep range only; keep_lo / keep_n come back as the
 // range this trace's stores obey — FArgs' own, or every bin for a non-finite trace — for f_inverse_input.
 // PK: the split's products in batches (cx_mul_batch)
+// PHASES = false (kCfgKeepPhases, "kept phases"): the phases are left where they are — no arctangents, no unwrap, no
+// store to A.ph_out (never dereferenced), no phase of bin N, and the sums are the amplitudes' alone.  Everything else is
+// the same instructions on the same values: spectrum, amplitudes and amplitude sums are the bits of the form that
+// computes phases.
 template <class P, bool AMP_PHASE, bool CMASK = false, bool SUMS = false, bool WC = false, bool STORE_FFT = true, bool BAND = false,
-          bool KEEP = false, bool PK = false>
+          bool KEEP = false, bool PK = false, bool PHASES = true>
 __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, const cx *wg_s,
                                                     const float *mask, size_t p, const FArgs &A,
                                                     int lane, FSums<P> *sums = nullptr, int *keep_lo = nullptr,
@@ -1109,8 +1131,9 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
     constexpr int N = P::N, NG = P::NG;
     static_assert(NG % 2 == 0, "pair ownership splits the groups in halves");
     const int nf = N + 1;
-    const float kPi = 3.14159274101257324219f, kTwoPi = 2.0f * kPi;
-    constexpr bool want_phase = AMP_PHASE;
+    [[maybe_unused]] const float kPi = 3.14159274101257324219f, kTwoPi = 2.0f * kPi;
+    constexpr bool want_phase = AMP_PHASE && PHASES;
+    static_assert(PHASES || AMP_PHASE, "kept phases: a form of the launches that write amplitudes");
     cx wl[4];
     if constexpr (WC) {
         const cx t = w2n_s[lane];
@@ -1122,10 +1145,10 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
 #pragma unroll
         for (int c = 0; c < 4; ++c) wl[c] = w2n_s[4 * lane + c];
     }
-    float carry = 0.0f;       // sum of adjusted differences of all previous groups
-    float prev_tail = 0.0f;   // raw phase of the last bin of the previous group
-    float first = 0.0f;       // raw phase of bin 0
-    float last_unwrapped = 0.0f, last_raw = 0.0f;
+    [[maybe_unused]] float carry = 0.0f;       // sum of adjusted differences of all previous groups
+    [[maybe_unused]] float prev_tail = 0.0f;   // raw phase of the last bin of the previous group
+    [[maybe_unused]] float first = 0.0f;       // raw phase of bin 0
+    [[maybe_unused]] float last_unwrapped = 0.0f, last_raw = 0.0f;
     // nat(256 g + 4 lane + c) = 256 g + fb[c];  nat(N - 256 g - 4 lane - c) = mb[c] - 256 g
     int fb[4], mb[4];
 #pragma unroll
@@ -1198,6 +1221,8 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
                 }
             }
         }
+        // kept phases: the sums' LDS reads go out here, in front of the multiplier and the square roots
+        if constexpr (SUMS && !want_phase) sums->template begin<false>(g, lane);
         // KEEP: the amplitude quads go to the keep range's bins below N as a window (FRow; bin N: lane 0, below)
         const unsigned amp_bytes = kn < N - klo ? 4u * (unsigned)kn : (N > klo ? 4u * (unsigned)(N - klo) : 0u);
         float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // the stored amplitudes (AMP_PHASE)
@@ -1285,6 +1310,8 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
                 last_raw = prev_tail;
             }
             if constexpr (SUMS) sums->group(g, a, y, lane);
+        } else if constexpr (SUMS) {
+            sums->template group<false>(g, a, a, lane);
         }
     }
     if constexpr (KEEP) {
@@ -1318,6 +1345,8 @@ __device__ __forceinline__ void f_spectrum_epilogue(cx *buf, const cx *w2n_s, co
                 sums->nyq_a += aN;
                 sums->nyq_p += last_unwrapped + d;
             }
+        } else if constexpr (SUMS) {
+            sums->nyq_a += aN;
         }
     }
 }
@@ -1587,10 +1616,12 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     constexpr bool BAND = (CFG & kCfgBand) != 0 && CMASK;
     constexpr bool KEEP = (CFG & kCfgKeep) != 0;
     constexpr bool LOW = (CFG & kCfgLow) != 0;
+    constexpr bool PHASES = (CFG & kCfgKeepPhases) == 0;
+    static_assert(PHASES || (LOW && (CFG & kCfgBar) != 0 && P::T1_COMPACT), "kept phases: the pruned nt = 4096 builds with the store barriers");
     static_assert(!KEEP || MODE == kPipe, "the keep range is the fused chain's");
     static_assert(!LOW || KEEP, "the pruned inverse input needs the keep range");
     static_assert(!SUMS || (MODE == kPipe && AMP_PHASE && (CFG & kCfgBar) != 0), "sums: fused chain, block-uniform trace loop");
-    constexpr int ME = P::mask_entries(CFG & ~(kCfgKeep | kCfgLow));
+    constexpr int ME = P::mask_entries(CFG & ~(kCfgKeep | kCfgLow | kCfgKeepPhases));
     const int nf = N + 1;
     const int lane = lane_id();
     const int wib = THZ_UNIFORM((int)(threadIdx.x >> 6));
@@ -1803,7 +1834,7 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     auto part_b = [&]() {
         if constexpr (MODE != kInv) {
             int keep_lo = 0, keep_n = kFKeepAll;  // MODE == kPipe: this trace's keep range (every bin if it is not finite)
-            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND, KEEP, PKB>(
+            f_spectrum_epilogue<P, AMP_PHASE, CMASK, SUMS, TC, MODE != kPipe, BAND, KEEP, PKB, PHASES>(
                 buf, launder_uniform((const cx *)w2n_s), launder_uniform((const cx *)wg_s), mask_l, p, A, lane, &sums, &keep_lo, &keep_n);
             if constexpr (MODE == kPipe) {
                 cx r[C1][R1];
@@ -1875,7 +1906,7 @@ __global__ __launch_bounds__(512) void k_f(FArgs A, FTables T)
     if constexpr ((CFG & kCfgBar) != 0) {
         if (pre_edge && post_edge && all_staged) trace_loop(FTrue{}, FTrue{});
         else trace_loop(FFalse{}, FTrue{});
-        if constexpr (SUMS) sums.finish(A.sum_partial + (size_t)blockIdx.x * (size_t)(2 * nf), nf, lane);
+        if constexpr (SUMS) sums.template finish<PHASES>(A.sum_partial + (size_t)blockIdx.x * (size_t)(PHASES ? 2 * nf : nf), nf, lane);
     } else {
         if (pre_edge && post_edge && all_staged) trace_loop(FTrue{}, FFalse{});
         else trace_loop(FFalse{}, FFalse{});

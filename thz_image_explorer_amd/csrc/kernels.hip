@@ -2394,11 +2394,17 @@ static size_t f_grid(size_t npix)
 // this thread's latest fused (kPipe) k_f launch — a session's recompute follows that launch with a forward transform of
 // the mean trace, which is not recorded.  Not part of the C ABI of include/thzgpu.h.
 thread_local int g_f_last_cfg = -1;
+// ... and whether that launch left the phases alone (fft_f.hpp, "kept phases"): 0 or 1.  The kCfgKeepPhases bit is not
+// part of g_f_last_cfg: a launch records the same bits there whether or not it computes phases.  Same status.
+thread_local int g_f_last_phases_kept = 0;
 
 template <class PL, int MODE, int CFG>
 static void launch_f(hipStream_t st, const PlanDev &P, const FArgs &A)
 {
-    if constexpr (MODE == kPipe) g_f_last_cfg = CFG;
+    if constexpr (MODE == kPipe) {
+        g_f_last_cfg = CFG & ~kCfgKeepPhases;
+        g_f_last_phases_kept = (CFG & kCfgKeepPhases) ? 1 : 0;
+    }
     const unsigned kBlock = f_block_threads<PL, CFG>();
     const size_t lds = PL::lds_bytes((int)(kBlock / kWave), CFG);
     const size_t g = f_grid<PL, MODE, CFG>(A.npix);
@@ -2443,8 +2449,11 @@ static bool f_low_fits(const PlanDev &P, const FArgs &A)
     return true;
 }
 
+// keep_phases (kPipe): ph_out holds this launch's phases already.  Honoured by the kCfgLow builds alone — a launch with
+// a keep range whose band fits (f_low_fits), with the store barriers on; every other launch computes and writes them
+// as if it had not been told (g_f_last_phases_kept says which ran).
 template <int MODE>
-static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool amp_phase)
+static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool amp_phase, bool keep_phases = false)
 {
     const int bar = f_bar_mode() ? kCfgBar : 0;
     if constexpr (MODE == kInv) {
@@ -2459,6 +2468,15 @@ static void dispatch_f(hipStream_t st, const PlanDev &P, const FArgs &A, bool am
                 constexpr int K = kCfgKeep | kCfgAmpPhase;
                 constexpr int L = K | kCfgLow | kCfgBar;
                 const bool low = f_low_fits(P, A);
+                if (low && bar && keep_phases) {
+                    constexpr int LP = L | kCfgKeepPhases;
+                    const bool band = A.cmask && f_band_fits(P, A.band_lo4, A.band_n);
+                    if (A.sum_partial && band) { launch_f<FPlan4096, MODE, LP | kCfgCMask | kCfgSums | kCfgBand>(st, P, A); return; }
+                    if (A.sum_partial && !A.cmask) { launch_f<FPlan4096, MODE, LP | kCfgSums>(st, P, A); return; }
+                    if (!A.sum_partial && A.cmask) { launch_f<FPlan4096, MODE, LP | kCfgCMask>(st, P, A); return; }
+                    if (!A.sum_partial) { launch_f<FPlan4096, MODE, LP>(st, P, A); return; }
+                    // (a complex multiplier with the sums whose band does not fit the band-limited table has no kCfgLow build)
+                }
                 if (A.sum_partial) {
                     if (A.cmask && f_band_fits(P, A.band_lo4, A.band_n)) {
                         if (low) launch_f<FPlan4096, MODE, L | kCfgCMask | kCfgSums | kCfgBand>(st, P, A);
@@ -2985,12 +3003,14 @@ size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4
 
 // the fused chains that honour a keep range: the F family's (with fft_out, amp_out and ph_out, which its callers require)
 bool pipeline_keeps_range(const PlanDev &P) { return P.family == kFamilyF; }
+bool pipeline_kept_phases() { return g_f_last_phases_kept == 1; }
 
 void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float *raw,
                      const float *pre_win, const float *mask, const float *post_win, c32 *fft_out,
                      float *amp_out, float *ph_out, float *data_out, float *img, const c32 *cmask,
-                     float *sum_partial, int band_lo4, int band_n, int keep_lo4, int keep_n)
+                     float *sum_partial, int band_lo4, int band_n, int keep_lo4, int keep_n, bool keep_phases)
 {
+    g_f_last_phases_kept = 0;
     if (P.family == kFamilyF && fft_out && amp_out && ph_out) {
         FArgs A{};
         A.npix = npix; A.in = raw; A.pre_win = pre_win; A.fft_out = reinterpret_cast<cx *>(fft_out); A.amp_out = amp_out;
@@ -3003,7 +3023,7 @@ void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float 
             A.keep_lo4 = keep_lo4 < P.nf ? keep_lo4 : (P.nf + 3) & ~3;
             A.keep_n = keep_n < kFKeepAll ? keep_n : kFKeepAll;
         }
-        dispatch_f<kPipe>(st, P, A, true);
+        dispatch_f<kPipe>(st, P, A, true, keep_phases);
         return;
     }
     const bool ph_plan = (P.family == kFamilyFB2 || P.family == kFamilyFB4 || P.family == kFamilyFB8) && P.half_n;

@@ -144,12 +144,18 @@ void launch_fft_inv(hipStream_t st, const PlanDev &P, size_t npix, const c32 *ff
 // keep_lo4 / keep_n (multiples of 4): the launch must store the bins [keep_lo4, keep_lo4 + keep_n) of fft_out and
 // amp_out and may leave the others untouched (fft_f.hpp, "keep range"); keep_n < 0 = every bin.  Honoured by the plans
 // pipeline_keeps_range() names; every other plan writes everything.
+// keep_phases: ph_out already holds the phases this launch would write (they depend on raw and pre_win alone); a launch
+// that can then leaves ph_out untouched and its sum rows are nf floats long (fft_f.hpp, "kept phases") —
+// pipeline_kept_phases() says whether it did; every other launch computes phases as if it had not been told.
 size_t pipeline_sum_rows(const PlanDev &P, size_t npix, bool cmask, int band_lo4 = 0, int band_n = 0);
 bool pipeline_keeps_range(const PlanDev &P);
 void launch_pipeline(hipStream_t st, const PlanDev &P, size_t npix, const float *raw,
                      const float *pre_win, const float *mask, const float *post_win, c32 *fft_out,
                      float *amp_out, float *ph_out, float *data_out, float *img, const c32 *cmask = nullptr,
-                     float *sum_partial = nullptr, int band_lo4 = 0, int band_n = 0, int keep_lo4 = 0, int keep_n = -1);
+                     float *sum_partial = nullptr, int band_lo4 = 0, int band_n = 0, int keep_lo4 = 0, int keep_n = -1,
+                     bool keep_phases = false);
+// whether this thread's latest launch_pipeline left ph_out alone
+bool pipeline_kept_phases();
 // The Tilt stage's re-laying (launch_tilt) as a gather in the fused chain's forward loads (fft_fbp.hpp, TILT): the
 // source traces on their own axis, the tail taper, and every pixel's insert index on the extended axis
 struct FBPTilt {

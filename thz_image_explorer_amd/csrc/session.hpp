@@ -112,6 +112,20 @@ struct thz_session {
     bool zeros_known = false;
     size_t zero_lo = 0, zero_hi = 0;
     unsigned long zero_gen = 0;  // the src_gen the knowledge belongs to
+    // Whether d_ph holds the unwrapped phases of the current source traces under the pre-transform multiplier
+    // phase_pre: they are those of FFT(pre x), in front of every Frequency-domain multiplier, so a recompute that moves
+    // the Frequency Band Pass, a plugin or the post Time Band Pass would write the bits that are there already.  The
+    // next fused launch is then told to leave them alone (fft_f.hpp, "kept phases"); where it carries the in-launch sums
+    // it leaves the phase half of d_msum out as well, which comes from d_phsum — a copy apart, like d_tiltsum, because
+    // session_means works on d_msum in place and a group all-reduces it.  phases_known = false: nothing is known, the
+    // next launch computes and writes them.  session_enqueue is d_ph's only writer; thz_session_buffer drops the
+    // knowledge when it hands out d_ph or the raw cube.
+    bool phases_known = false;
+    unsigned long phase_gen = 0;     // the src_gen the knowledge belongs to
+    std::vector<float> phase_pre;    // the pre-transform multiplier of the launch that wrote them
+    float *d_phsum = nullptr;        // (nf) that launch's in-launch sums of the phases, if it carried sums
+    size_t phsum_floats = 0;
+    bool phsum_valid = false;
     const float *d_src = nullptr;  // what the fft stage read: d_raw, d_scaled or d_tilt (extended axis); null while a
                                    //   one-launch tilted chain's extended cube has not been asked for
     // ---- regions of interest (session_roi.cpp)

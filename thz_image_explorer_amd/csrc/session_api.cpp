@@ -100,7 +100,7 @@ void thz_session_destroy(thz_session *s)
     for (void *p : {(void *)s->d_raw, (void *)s->d_fft, (void *)s->d_amp, (void *)s->d_ph, (void *)s->d_data,
                     (void *)s->d_img, (void *)s->d_avg, (void *)s->d_vec, (void *)s->d_tilt, (void *)s->d_ins,
                     (void *)s->d_opacity, (void *)s->d_deconv, (void *)s->d_deconv_img, (void *)s->d_scaled,
-                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_carry_in, (void *)s->d_carry_out})
+                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_phsum, (void *)s->d_carry_in, (void *)s->d_carry_out})
         if (p) (void)hipFree(p);
     for (ResidentMaps &m : s->maps)
         if (m.d) (void)hipFree(m.d);
@@ -304,6 +304,10 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     const float *const fft_before = s->d_fft;
     const size_t pix_before = s->out_pix, nt_before = s->nt_out;
     s->zeros_known = false;
+    // ... and so for what is known of the phases in d_ph
+    const bool phases_before = s->phases_known && s->phase_gen == s->src_gen;
+    const float *const ph_before = s->d_ph;
+    s->phases_known = false;
     s->have_outputs = false;  // the grid may change under the buffers below
     s->have_last_cfg = false;
     s->deconv_current = false;
@@ -506,6 +510,17 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
         keep.lo = std::min((size_t)band_lo, s->zero_lo);
         keep.hi = std::max((size_t)band_hi, s->zero_hi);
     }
+    // The phases are those of FFT(pre x), in front of the multiplier: where d_ph holds them for these source traces and
+    // this very pre-transform multiplier, the launch is told to leave them alone (session.hpp; fft_f.hpp, "kept
+    // phases") — what a drag on the Frequency Band Pass, a plugin or the post Time Band Pass comes to.  A launch that
+    // carries the sums then needs the kept phase sums.  THZ_F_KEEP_ZEROS=0 keeps its meaning;
+    // THZ_F_KEEP_PHASES=0: developer knob, every launch computes and writes the phases.
+    const bool phsum_kept = s->phsum_valid && s->phsum_floats == nf;
+    bool keep_phases = phases_before && !keep.all && !tilted && s->d_ph == ph_before && s->out_pix == pix_before && s->nt_out == nt_before
+                       && s->phase_pre.size() == nt_cur && std::memcmp(s->phase_pre.data(), pre.data(), nt_cur * sizeof(float)) == 0
+                       && (!s->msum_fast || phsum_kept);
+    if (const char *e = getenv("THZ_F_KEEP_PHASES")) keep_phases = keep_phases && atoi(e) != 0;
+    keep.phases = keep_phases;
     if (fused_tilt) {
         io.d_raw = nullptr;
         thz_tilt_src ts{};
@@ -529,6 +544,29 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
         s->zeros_known = true;
         s->zero_lo = (size_t)band_lo; s->zero_hi = (size_t)band_hi;
         s->zero_gen = s->src_gen;
+    }
+    // d_phsum follows the launches that carry sums: the phase half of d_msum of the one that computed the phases, handed
+    // on to those that kept them (apart from d_msum, which session_means scales and a group all-reduces in place)
+    if (keep.phases_honoured) {
+        if (s->msum_fast)
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_msum + nt_cur + nf, s->d_phsum, nf * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        s->phases_known = true;  // as before this launch: same generation, same multiplier
+    } else if (keep.honoured && !tilted) {  // (a launch of a family that was not told leaves nothing known)
+        s->phsum_valid = false;
+        if (s->msum_fast) {
+            if (s->phsum_floats != nf) {
+                s->phsum_floats = 0;
+                if (int rc = dev_alloc(ctx, &s->d_phsum, nf)) return rc;
+                s->phsum_floats = nf;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_phsum, s->d_msum + nt_cur + nf, nf * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+            s->phsum_valid = true;
+        }
+        s->phase_pre = pre;
+        s->phase_gen = s->src_gen;
+        s->phases_known = true;
+    } else {
+        s->phsum_valid = false;
     }
     if (s->msum_passes) {
         if (int rc = thz_pixel_sum(ctx, npix, nf, 2, s->d_fft, s->d_msum + nt_cur)) return rc;
@@ -697,6 +735,8 @@ void *thz_session_buffer(thz_session *s, int which)
 {
     // a caller that holds the pointer may write: nothing is known of the two arrays' zeros any more (session.hpp)
     if (s && (which == THZ_BUF_FFT || which == THZ_BUF_AMPLITUDES)) s->zeros_known = false;
+    // ... nor of the phases, which a new raw cube would change as well
+    if (s && (which == THZ_BUF_PHASES || which == THZ_BUF_RAW)) s->phases_known = false;
     return const_cast<void *>(session_buffer_ro(s, which));
 }
 
