@@ -48,12 +48,7 @@ void thz_destroy(thz_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-    if (ctx->d_big) (void)hipFree(ctx->d_big);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->tilt_scratch) (void)hipFree(ctx->tilt_scratch);
     for (auto &g : ctx->dc_graph) g.drop();
-    ctx->drop_dc_tables();
     for (auto &b : ctx->dc_pool) (void)hipFree(b.p);
     for (auto &r : ctx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : ctx->pool) (void)hipEventDestroy(e);
@@ -76,12 +71,8 @@ int thz_release_scratch(thz_ctx *ctx)
     ctx->drop_dc_tables();
     for (auto &b : ctx->dc_pool) (void)hipFree(b.p);
     ctx->dc_pool.clear();
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    if (ctx->tilt_scratch) (void)hipFree(ctx->tilt_scratch);
-    ctx->tilt_scratch = nullptr;
-    ctx->tilt_scratch_floats = 0;
+    ctx->ws.drop(ctx);
+    ctx->tilt_scratch.drop(ctx);
     return THZ_OK;
 }
 
@@ -171,9 +162,11 @@ int thz_set_time_axis(thz_ctx *ctx, const float *time, size_t nt)
     const size_t n_ones = (size_t)(H.nf + 1) / 2;  // nf floats of 1.0, counted in c32 units
     const size_t n_p1 = H.p_t1.size(), n_p2 = H.p_t2.size();
     const size_t total = n_tw + n_sp + n_ch + n_bf + n_f1 + n_f2 + n_fw + n_ones + n_p1 + n_p2;
-    c32 *d = nullptr;
+    // the new tables are built beside the standing ones and replace them only when everything has succeeded: a
+    // failure leaves the standing plan usable
+    DevBuf<c32> tables, big;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMalloc((void **)&d, total * sizeof(c32)));
+    if (int rc = tables.exact(ctx, total)) return rc;
     std::vector<c32> pack;
     pack.reserve(total);
     pack.insert(pack.end(), H.tw.begin(), H.tw.end());
@@ -186,21 +179,16 @@ int thz_set_time_axis(thz_ctx *ctx, const float *time, size_t nt)
     pack.insert(pack.end(), n_ones, c32{1.0f, 1.0f});
     pack.insert(pack.end(), H.p_t1.begin(), H.p_t1.end());
     pack.insert(pack.end(), H.p_t2.begin(), H.p_t2.end());
-    hipError_t e = hipMemcpy(d, pack.data(), total * sizeof(c32), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(ctx, THZ_ERR_HIP, std::string("table upload: ") + hipGetErrorString(e));
-    }
-    c32 *d_big = nullptr;
-    if (H.big && hipMalloc((void **)&d_big, (size_t)H.big_waves * (size_t)H.lds_per_wave) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d);
-        return fail(ctx, THZ_ERR_HIP, "scratch of the long-trace transform: allocation failed");
-    }
-    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-    if (ctx->d_big) (void)hipFree(ctx->d_big);
-    ctx->d_tables = d;
-    ctx->d_big = d_big;
+    hipError_t e = hipMemcpy(tables, pack.data(), total * sizeof(c32), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(ctx, THZ_ERR_HIP, std::string("table upload: ") + hipGetErrorString(e));
+    if (H.big)
+        if (int rc = big.exact(ctx, (size_t)H.big_waves * (size_t)H.lds_per_wave / sizeof(c32))) {  // (whole c32: plan_host.hpp)
+            (void)hipGetLastError();
+            return rc;
+        }
+    ctx->d_tables = std::move(tables);
+    ctx->d_big = std::move(big);
+    c32 *const d = ctx->d_tables;
     ctx->plan_h = H;
     const size_t o_f = n_tw + n_sp + n_ch + n_bf;
     ctx->plan_d = plan_dev(H, d, n_sp ? d + n_tw : nullptr, n_ch ? d + n_tw + n_sp : nullptr,
@@ -208,7 +196,7 @@ int thz_set_time_axis(thz_ctx *ctx, const float *time, size_t nt)
                            n_f2 ? d + o_f + n_f1 : nullptr, n_fw ? d + o_f + n_f1 + n_f2 : nullptr,
                            reinterpret_cast<const float *>(d + o_f + n_f1 + n_f2 + n_fw),
                            n_p1 ? d + o_f + n_f1 + n_f2 + n_fw + n_ones : nullptr,
-                           n_p2 ? d + o_f + n_f1 + n_f2 + n_fw + n_ones + n_p1 : nullptr, d_big);
+                           n_p2 ? d + o_f + n_f1 + n_f2 + n_fw + n_ones + n_p1 : nullptr, ctx->d_big);
     ctx->plan_allow_f = ctx->allow_f;
     ctx->plan_allow_p = ctx->allow_p;
     ctx->time.assign(time, time + nt);
@@ -334,15 +322,12 @@ int thz_reference_spectrum(thz_ctx *ctx, const float *scan_time, size_t nt, cons
     if (!ctx->have_plan || ctx->time.size() != nt || std::memcmp(ctx->time.data(), scan_time, nt * sizeof(float)) != 0)
         if (int rc = thz_set_time_axis(ctx, scan_time, nt)) return rc;
     const size_t nf = nt / 2 + 1;
-    float *d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d, (nt + 2 * nf) * sizeof(float)));
-    int rc = thz_memcpy_h2d(ctx, d, reference_out, nt * sizeof(float));
-    if (!rc) rc = thz_fft(ctx, 1, d, nullptr, nullptr, nullptr, nullptr, d + nt, d + nt + nf, nullptr);
-    if (!rc) rc = thz_memcpy_d2h(ctx, amplitudes, d + nt, nf * sizeof(float));
-    if (!rc) rc = thz_memcpy_d2h(ctx, phases, d + nt + nf, nf * sizeof(float));
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
+    CallBuf<float> d(ctx);
+    if (int rc = d.alloc(nt + 2 * nf)) return rc;
+    if (int rc = thz_memcpy_h2d(ctx, d, reference_out, nt * sizeof(float))) return rc;
+    if (int rc = thz_fft(ctx, 1, d, nullptr, nullptr, nullptr, nullptr, d + nt, d + nt + nf, nullptr)) return rc;
+    if (int rc = thz_memcpy_d2h(ctx, amplitudes, d + nt, nf * sizeof(float))) return rc;
+    return thz_memcpy_d2h(ctx, phases, d + nt + nf, nf * sizeof(float));
 }
 
 int thz_host_optical_properties(const float *sample_amp, const float *sample_phase, const float *ref_amp,
@@ -416,15 +401,12 @@ int thz_polar_ifft(thz_ctx *ctx, const float *amp, const float *phase, int zero_
         spec[2 * k + 1] = amp[k] * std::sin(phase[k]);
     }
     if (zero_dc_imag) spec[1] = 0.0f;
-    float *d = nullptr;
     const size_t o = (2 * nf + 3) & ~(size_t)3;  // the trace starts 16-byte aligned, like a cube's first row
-    HIP_TRY(ctx, hipMalloc((void **)&d, (o + nt) * sizeof(float)));
-    int rc = thz_memcpy_h2d(ctx, d, spec.data(), 2 * nf * sizeof(float));
-    if (!rc) rc = thz_ifft(ctx, 1, d, nullptr, d + o, nullptr);
-    if (!rc) rc = thz_memcpy_d2h(ctx, out, d + o, nt * sizeof(float));
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
+    CallBuf<float> d(ctx);
+    if (int rc = d.alloc(o + nt)) return rc;
+    if (int rc = thz_memcpy_h2d(ctx, d, spec.data(), 2 * nf * sizeof(float))) return rc;
+    if (int rc = thz_ifft(ctx, 1, d, nullptr, d + o, nullptr)) return rc;
+    return thz_memcpy_d2h(ctx, out, d + o, nt * sizeof(float));
 }
 
 int thz_pipeline(thz_ctx *ctx, size_t npix, const float *d_raw, const float *d_pre_win,
@@ -501,7 +483,7 @@ int pipeline_ex_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, size_
     float *d_partial = nullptr;
     if (sum_rows) {
         if (int rc = ensure_ws(ctx, sum_rows * 2 * nf * sizeof(float))) return rc;
-        d_partial = reinterpret_cast<float *>(ctx->ws);
+        d_partial = ctx->ws.as<float>();
     }
     {
         StageTimer t(ctx, THZ_STAGE_PIPELINE);
@@ -555,7 +537,7 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
         const size_t src_rows = src->d_src_sum ? tilt_sum_rows(npix) : 0;
         if (sum_rows || src_rows)
             if (int rc = ensure_ws(ctx, (sum_rows * 2 * nf + src_rows * nt) * sizeof(float))) return rc;
-        float *d_partial = sum_rows ? reinterpret_cast<float *>(ctx->ws) : nullptr;
+        float *d_partial = sum_rows ? ctx->ws.as<float>() : nullptr;
         {
             StageTimer t(ctx, THZ_STAGE_PIPELINE);
             launch_pipeline_tilted(ctx->stream, ctx->plan_d, npix, TL, io->d_pre_win, io->d_fd_mask, io->d_post_win,
@@ -567,7 +549,7 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
             StageTimer t(ctx, THZ_STAGE_MEAN);
             if (d_partial) launch_sum_rows_f64(ctx->stream, d_partial, sum_rows, 2 * nf, io->d_sums);
             if (src->d_src_sum &&
-                !launch_tilt_sum(ctx->stream, npix, (int)nt, TL, reinterpret_cast<float *>(ctx->ws) + sum_rows * 2 * nf, src->d_src_sum))
+                !launch_tilt_sum(ctx->stream, npix, (int)nt, TL, ctx->ws.as<float>() + sum_rows * 2 * nf, src->d_src_sum))
                 return fail(ctx, THZ_ERR_INVALID, "thz_pipeline_tilted: the source sum of a one-launch plan needs nt <= 2048");
             if (int rc = check_launch(ctx)) return rc;
         }
@@ -578,16 +560,7 @@ int pipeline_tilted_band(thz_ctx *ctx, size_t npix, const thz_pipeline_io *io, c
         return THZ_OK;
     }
     // every other plan: the staged form — the re-laid traces into scratch of the context, the chain on them
-    if (ctx->tilt_scratch_floats < npix * nt) {
-        if (ctx->tilt_scratch) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipFree(ctx->tilt_scratch));
-            ctx->tilt_scratch = nullptr;
-            ctx->tilt_scratch_floats = 0;
-        }
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->tilt_scratch, npix * nt * sizeof(float)));
-        ctx->tilt_scratch_floats = npix * nt;
-    }
+    if (int rc = ctx->tilt_scratch.grow(ctx, npix * nt)) return rc;
     if (int rc = thz_tilt_apply(ctx, npix, src->d_src, src->nt_in, src->d_taper, src->d_insert_index, nt, ctx->tilt_scratch)) return rc;
     thz_pipeline_io staged = *io;
     staged.d_raw = ctx->tilt_scratch;
@@ -644,7 +617,7 @@ int thz_pixel_mean(thz_ctx *ctx, size_t nx, size_t ny, size_t len, int ncomp, co
     const size_t L = len * (size_t)ncomp;
     if (int rc = ensure_ws(ctx, ny * L * sizeof(float))) return rc;
     StageTimer t(ctx, THZ_STAGE_MEAN);
-    float *acc = reinterpret_cast<float *>(ctx->ws);
+    float *acc = ctx->ws.as<float>();
     launch_sum_axis0(ctx->stream, d_arr, nx, ny * L, (float)nx, acc);
     launch_sum_axis0(ctx->stream, acc, ny, L, (float)ny, d_out);
     return check_launch(ctx);
@@ -670,7 +643,7 @@ int pixel_sum_rows(thz_ctx *ctx, const float *d_arr, const uint32_t *d_list, siz
     const size_t ws_floats = pixel_sum_ws_floats(npix, L);
     if (ws_floats)
         if (int rc = ensure_ws(ctx, ws_floats * sizeof(float))) return rc;
-    launch_pixel_sum_rows(ctx->stream, d_arr, d_list, npix, L, reinterpret_cast<float *>(ctx->ws), d_out);
+    launch_pixel_sum_rows(ctx->stream, d_arr, d_list, npix, L, ctx->ws.as<float>(), d_out);
     return check_launch(ctx);
 }
 
@@ -705,7 +678,7 @@ int thz_roi_mask(thz_ctx *ctx, const uint64_t *poly_xy, size_t n_vertices, uint6
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, poly.data(), poly.size() * sizeof(uint64_t),
                                 hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `poly` is a stack-lifetime vector
-    launch_roi_mask(ctx->stream, reinterpret_cast<const uint64_t *>(ctx->ws), (int)n_vertices, x_min,
+    launch_roi_mask(ctx->stream, ctx->ws.as<const uint64_t>(), (int)n_vertices, x_min,
                     x_max, y_min, y_max, x_size, y_size, d_mask);
     if (int rc = check_launch(ctx)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // workspace is reused by the next call
@@ -738,7 +711,7 @@ int thz_roi_mean(thz_ctx *ctx, const float *d_arr, size_t shape0, size_t shape1,
     if (int rc = ensure_ws(ctx, list.size() * sizeof(uint32_t))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, list.data(), list.size() * sizeof(uint32_t),
                                 hipMemcpyHostToDevice, ctx->stream));
-    launch_gather_sum(ctx->stream, d_arr, len, reinterpret_cast<const uint32_t *>(ctx->ws), count,
+    launch_gather_sum(ctx->stream, d_arr, len, ctx->ws.as<const uint32_t>(), count,
                       sum_only ? 0.0f : (float)count, d_out);
     if (int rc = check_launch(ctx)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

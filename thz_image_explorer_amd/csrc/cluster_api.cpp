@@ -68,7 +68,7 @@ int unfinished(thz_session *s, const char *why)
 int fetch_row(thz_ctx *ctx, const SessionMatrix &m, size_t pixel, float *row)
 {
     if (int rc = ensure_ws(ctx, m.L * sizeof(float))) return rc;
-    launch_cluster_row(ctx->stream, PcaView{m.d, m.npix, (int)m.L, m.row_stride, m.col_step, nullptr}, pixel, static_cast<float *>(ctx->ws));
+    launch_cluster_row(ctx->stream, PcaView{m.d, m.npix, (int)m.L, m.row_stride, m.col_step, nullptr}, pixel, ctx->ws.as<float>());
     if (int rc = check_launch(ctx)) return rc;
     return thz_memcpy_d2h(ctx, row, ctx->ws, m.L * sizeof(float));
 }

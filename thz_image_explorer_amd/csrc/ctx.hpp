@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/thzgpu.h"
 
+#include "dev_buf.hpp"
 #include "kernels.hpp"
 #include "plan_host.hpp"
 
@@ -21,16 +22,14 @@ struct thz_ctx {
     std::vector<float> time, freq;
     PlanHost plan_h;
     PlanDev plan_d{};
-    c32 *d_tables = nullptr;  // one allocation: tw | tw_split | chirp_conj | bfft
-    c32 *d_big = nullptr;     // global scratch of a plan whose buffers do not fit LDS (plan_d.big_scratch), or null
+    DevBuf<c32> d_tables;     // one allocation: tw | tw_split | chirp_conj | bfft
+    DevBuf<c32> d_big;        // global scratch of a plan whose buffers do not fit LDS (plan_d.big_scratch), or null
     bool have_plan = false;
     bool allow_f = true, allow_p = true;  // thz_set_kernel_family
     bool plan_allow_f = true, plan_allow_p = true;  // the switches the current plan was built under
     hipStream_t aux_streams[3] = {nullptr, nullptr, nullptr};  // the deconvolution's extra chains (created on first use)
-    void *ws = nullptr;  // scratch workspace (pixel means, ROI lists)
-    size_t ws_bytes = 0;
-    float *tilt_scratch = nullptr;  // thz_pipeline_tilted on a plan without the gather: the re-laid traces
-    size_t tilt_scratch_floats = 0;
+    DevBuf<unsigned char> ws;     // scratch workspace (pixel means, ROI lists), grow-only, in bytes
+    DevBuf<float> tilt_scratch;   // thz_pipeline_tilted on a plan without the gather: the re-laid traces (grow-only)
     // device blocks of the last thz_deconvolve call, kept for the next one: a call of the same geometry then neither
     // allocates nor frees (eleven hipMalloc + hipFree pairs measured 0.8 ms of a 10 ms call); blocks a call did
     // not use are freed at its end, so a change of geometry does not accumulate memory
@@ -72,34 +71,29 @@ struct thz_ctx {
     struct DcPlan {
         size_t M = 0;
         PlanHost H;
-        c32 *d_tw = nullptr;
+        DevBuf<c32> d_tw;
         size_t o1 = 0, o2 = 0, o3 = 0;
         bool f = false;
     } dc_plan;
     struct DcSpectra {
-        c32 *d_H = nullptr;
+        DevBuf<c32> d_H;
         size_t M = 0;
         unsigned bank_gen = 0;
         int b0 = -1, b1 = -1;
         // tables of the Parseval band energies (k_dc_energy_pv), one block: [t1 512][t2 64][hpm nb 1024] c32, then g
-        c32 *d_pv = nullptr;
+        DevBuf<c32> d_pv;
         size_t pv_g_off = 0;  // in c32 units from d_pv
         int pv_gstride = 0;
     } dc_spectra;
     // the spectra of a slab's traces between the energies phase and the recombination phase of a group's
     // Deconvolution stage (thz_dc_slab_energies / thz_dc_slab_combine, deconv_api.cpp)
     struct DcSlab {
-        c32 *d_spec = nullptr;
-        size_t cap = 0;            // entries allocated
+        DevBuf<c32> d_spec;        // grow-only
         size_t npix = 0, nk = 0;   // what it holds: npix rows of nk bins
         size_t M = 0;
     } dc_slab;
     void drop_dc_tables()
     {
-        if (dc_plan.d_tw) (void)hipFree(dc_plan.d_tw);
-        if (dc_spectra.d_H) (void)hipFree(dc_spectra.d_H);
-        if (dc_spectra.d_pv) (void)hipFree(dc_spectra.d_pv);
-        if (dc_slab.d_spec) (void)hipFree(dc_slab.d_spec);
         dc_plan = DcPlan{};
         dc_spectra = DcSpectra{};
         dc_slab = DcSlab{};
@@ -130,6 +124,11 @@ int thz_dc_slab_combine(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *
 int thz_dc_band_costs(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg, size_t nx, size_t ny, float dx, float dy,
                       std::vector<double> *costs);
 
+static_assert(kDevBufErrHip == THZ_ERR_HIP, "a failed allocation is a HIP failure of the C ABI");
+// a device block of one call on a context's stream (dev_buf.hpp)
+template <class T>
+using CallBuf = ScopedDevBuf<T, thz_ctx>;
+
 namespace thz_api {
 
 inline int fail(thz_ctx *ctx, int code, const std::string &msg)
@@ -151,19 +150,7 @@ inline int use_device(thz_ctx *ctx)
     return THZ_OK;
 }
 
-inline int ensure_ws(thz_ctx *ctx, size_t bytes)
-{
-    if (ctx->ws_bytes >= bytes) return THZ_OK;
-    if (ctx->ws) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(ctx->ws));
-        ctx->ws = nullptr;
-        ctx->ws_bytes = 0;
-    }
-    HIP_TRY(ctx, hipMalloc(&ctx->ws, bytes));
-    ctx->ws_bytes = bytes;
-    return THZ_OK;
-}
+inline int ensure_ws(thz_ctx *ctx, size_t bytes) { return ctx->ws.grow(ctx, bytes); }
 
 inline hipEvent_t pool_event(thz_ctx *ctx)
 {

@@ -298,7 +298,7 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
     // the tables of the padded length live in the context until M changes
     thz_ctx::DcPlan &PL = ctx->dc_plan;
     if (PL.M != M && phase != 2 && phase != 4) {
-        if (PL.d_tw) (void)hipFree(PL.d_tw);
+        PL.d_tw.drop(ctx);
         PL = thz_ctx::DcPlan{};
         // (M = 16384: the generic recombination's three LDS buffers are 192 KiB — its launch was refused with
         // "invalid argument" — so traces of more than 7694 samples are refused here, by name)
@@ -314,7 +314,7 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
         if (PL.f) pack.insert(pack.end(), H.f_t2.begin(), H.f_t2.end());
         PL.o3 = pack.size();
         if (PL.f) pack.insert(pack.end(), H.f_w2n.begin(), H.f_w2n.end());
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&PL.d_tw), pack.size() * sizeof(c32)));
+        if (int rc = PL.d_tw.exact(ctx, pack.size())) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(PL.d_tw, pack.data(), pack.size() * sizeof(c32), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pack goes out of scope
         H.f_t1.clear();  // offsets only from here on
@@ -343,8 +343,8 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
     const int nbs = b1 - b0;
     thz_ctx::DcSpectra &SP = ctx->dc_spectra;
     if (transforms && (!SP.d_H || SP.M != M || SP.bank_gen != ctx->dc_bank.gen || SP.b0 != b0 || SP.b1 != b1)) {
-        if (SP.d_H) (void)hipFree(SP.d_H);
-        if (SP.d_pv) (void)hipFree(SP.d_pv);
+        SP.d_H.drop(ctx);
+        SP.d_pv.drop(ctx);
         SP = thz_ctx::DcSpectra{};
         std::vector<double> trig(2 * M);  // cos | sin of -2 pi m / M
         for (size_t m = 0; m < M; ++m) {
@@ -356,7 +356,7 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
         float *d_filters = nullptr;
         HIP_TRY(ctx, mem.alloc(&d_trig, trig.size() * sizeof(double)));
         HIP_TRY(ctx, mem.alloc(&d_filters, (size_t)nbs * kDeconvTaps * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&SP.d_H), (size_t)nbs * nk * sizeof(c32)));
+        if (int rc = SP.d_H.exact(ctx, (size_t)nbs * nk)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(d_trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_filters, filters.data() + (size_t)b0 * kDeconvTaps,
                                     (size_t)nbs * kDeconvTaps * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -389,8 +389,7 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
             HIP_TRY(ctx, mem.alloc(&d_trig_e, trig_e.size() * sizeof(double)));
             HIP_TRY(ctx, mem.alloc(&d_halves, halves.size() * sizeof(float)));
             HIP_TRY(ctx, mem.alloc(&d_hht, (size_t)2 * nbs * 512 * sizeof(c32)));
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&SP.d_pv),
-                                   (n_tab + n_hpm) * sizeof(c32) + (size_t)nbs * gstride * sizeof(float)));
+            if (int rc = SP.d_pv.exact(ctx, n_tab + n_hpm + ((size_t)nbs * gstride + 1) / 2)) return rc;  // g: floats behind the c32
             SP.pv_g_off = n_tab + n_hpm;
             SP.pv_gstride = gstride;
             t1.insert(t1.end(), t2.begin(), t2.end());
@@ -412,15 +411,7 @@ int deconvolve_impl(thz_ctx *ctx, const thz_psf *psf, const thz_deconv_cfg *cfg,
     if (phase == 1) {
         // ---- a slab's spectra (kept in the context for phase 3) and its band energies, every band
         thz_ctx::DcSlab &S = ctx->dc_slab;
-        if (S.cap < npix_t * nk) {
-            if (S.d_spec) {
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                (void)hipFree(S.d_spec);
-            }
-            S = thz_ctx::DcSlab{};
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&S.d_spec), npix_t * nk * sizeof(c32)));
-            S.cap = npix_t * nk;
-        }
+        if (int rc = S.d_spec.grow(ctx, npix_t * nk)) return rc;
         S.npix = npix_t; S.nk = nk; S.M = M;
         launch_dc_fft(ctx->stream, P, npix_t, (int)nt, d_in, S.d_spec);
         dc_band_energies(ctx, P, npix_t, (int)nt, nbs, shift, (int)nk, d_in, S.d_spec, d_H, sp->d_energy);

@@ -32,13 +32,13 @@ struct thz_group_session {
     std::vector<thz_session *> sess;   // one per local member
     std::vector<size_t> x0, rows;      // one per rank
     int root_local = -1;               // index of rank 0 among the local members, -1: another process has it
-    // gathered copies on rank 0's device, allocated when first asked for
-    float *d_img = nullptr, *d_data = nullptr, *d_fft = nullptr, *d_amp = nullptr, *d_ph = nullptr;
-    size_t cap_img = 0, cap_data = 0, cap_fft = 0, cap_amp = 0, cap_ph = 0;  // floats allocated
+    // gathered copies on rank 0's device, allocated when first asked for (grow-only)
+    DevBuf<float> d_img, d_data, d_fft, d_amp, d_ph;
     // gathered arrival-time maps of the last thz_group_session_estimate_tilt (group_tilt.cpp), on rank 0's device:
-    // [index bits | offsets | values], cap_peak entries each of which the first peak_pix are the grid's
-    float *d_peak = nullptr;
-    size_t cap_peak = 0, peak_pix = 0;
+    // [index bits | offsets | values], peak_stride() entries each of which the first peak_pix are the grid's (grow-only)
+    DevBuf<float> d_peak;
+    size_t peak_pix = 0;
+    size_t peak_stride() const { return d_peak.count() / 3; }
     std::vector<size_t> cur_rows;      // rows of the outputs' grid per rank (the block grid behind a scaling stage)
     size_t cur_ny = 0;
     size_t cur_pix() const

@@ -104,16 +104,7 @@ static int dc_slabs(thz_group_session *gs, const thz_psf *psf, const thz_deconv_
     for (size_t i = 0; i < nl; ++i) {
         thz_session *s = gs->sess[i];
         GHIP_TRY(g, hipSetDevice(g->m[i].ctx->device));
-        const size_t n = pix_of(i) * nt;
-        if (s->deconv_floats != n) {
-            if (s->d_deconv) { (void)hipFree(s->d_deconv); s->d_deconv = nullptr; }
-            if (s->d_deconv_img) { (void)hipFree(s->d_deconv_img); s->d_deconv_img = nullptr; }
-            s->deconv_floats = 0;
-            if (hipMalloc((void **)&s->d_deconv, n * sizeof(float)) != hipSuccess
-                || hipMalloc((void **)&s->d_deconv_img, pix_of(i) * sizeof(float)) != hipSuccess)
-                return gfail(g, THZ_ERR_HIP, "thz_group_session_deconvolve: slab allocation failed");
-            s->deconv_floats = n;
-        }
+        if (int rc = session_size_deconv(s)) return gfail(g, rc, std::string("thz_group_session_deconvolve: ") + thz_last_error(s->ctx));
         if (int rc = bufs.alloc(i, &flag[i], sizeof(float), "thz_group_session_deconvolve: allocation failed")) return rc;
     }
     std::vector<int> rcs;

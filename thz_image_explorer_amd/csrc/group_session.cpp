@@ -109,24 +109,17 @@ static int group_means(thz_group_session *gs, const thz_chain_cfg *cfg, bool sin
 }
 
 // C1: one per-pixel result to rank 0, whose buffer grows when it is too small
-static int gather_buf(thz_group_session *gs, int which, size_t per_pix, float **d_dst, size_t *cap)
+static int gather_buf(thz_group_session *gs, int which, size_t per_pix, DevBuf<float> *d_dst)
 {
     thz_group *g = gs->g;
     std::vector<const float *> send;
     std::vector<size_t> counts((size_t)g->world);
     for (int q = 0; q < g->world; ++q) counts[(size_t)q] = gs->cur_rows[(size_t)q] * gs->cur_ny * per_pix;
     for (thz_session *s : gs->sess) send.push_back(static_cast<const float *>(session_buffer_ro(s, which)));
-    const size_t need = gs->cur_pix() * per_pix;
-    if (gs->root_local >= 0 && (!*d_dst || *cap < need)) {  // (a tilted cube's outputs are longer than the raw traces)
-        GHIP_TRY(g, hipSetDevice(g->m[(size_t)gs->root_local].ctx->device));
-        if (*d_dst) {
-            GHIP_TRY(g, hipStreamSynchronize(g->m[(size_t)gs->root_local].ctx->stream));
-            GHIP_TRY(g, hipFree(*d_dst));
-            *d_dst = nullptr;
-            *cap = 0;
-        }
-        GHIP_TRY(g, hipMalloc((void **)d_dst, need * sizeof(float)));
-        *cap = need;
+    if (gs->root_local >= 0) {  // (a tilted cube's outputs are longer than the raw traces)
+        thz_ctx *ctx = g->m[(size_t)gs->root_local].ctx;
+        GHIP_TRY(g, hipSetDevice(ctx->device));
+        if (int rc = d_dst->grow(ctx, gs->cur_pix() * per_pix)) return gfail(g, rc, std::string("gathered results: ") + thz_last_error(ctx));
     }
     return thz_group_gather(g, send.data(), counts.data(), *d_dst);
 }
@@ -137,11 +130,7 @@ void thz_group_session_destroy(thz_group_session *gs)
 {
     if (!gs) return;
     for (thz_session *s : gs->sess) thz_session_destroy(s);
-    if (gs->root_local >= 0) {
-        (void)hipSetDevice(gs->g->m[(size_t)gs->root_local].ctx->device);
-        for (float *p : {gs->d_img, gs->d_data, gs->d_fft, gs->d_amp, gs->d_ph, gs->d_peak})
-            if (p) (void)hipFree(p);
-    }
+    if (gs->root_local >= 0) (void)hipSetDevice(gs->g->m[(size_t)gs->root_local].ctx->device);
     delete gs;
 }
 
@@ -176,10 +165,9 @@ int thz_group_session_create(thz_group *g, size_t nx, size_t ny, size_t nt, cons
     gs->cur_rows = gs->rows;
     gs->cur_ny = ny;
     if (gs->root_local >= 0) {
-        if (hipSetDevice(g->m[(size_t)gs->root_local].ctx->device) != hipSuccess
-            || hipMalloc((void **)&gs->d_img, nx * ny * sizeof(float)) != hipSuccess)
+        thz_ctx *ctx = g->m[(size_t)gs->root_local].ctx;
+        if (hipSetDevice(ctx->device) != hipSuccess || gs->d_img.grow(ctx, nx * ny))
             return gfail(g, THZ_ERR_HIP, "gathered image: allocation failed");
-        gs->cap_img = nx * ny;
     }
     *out = own.release();
     return THZ_OK;
@@ -266,13 +254,13 @@ int thz_group_session_recompute(thz_group_session *gs, const thz_chain_cfg *cfg,
     if (!s0->rois.empty())
         if (int rc = group_roi_tail(gs, cfg, tail_only)) return rc;
     // C1: per-pixel results to rank 0
-    if (int rc = gather_buf(gs, THZ_BUF_IMG, 1, &gs->d_img, &gs->cap_img)) return rc;
+    if (int rc = gather_buf(gs, THZ_BUF_IMG, 1, &gs->d_img)) return rc;
     if (gather >= THZ_GATHER_TIME)
-        if (int rc = gather_buf(gs, THZ_BUF_DATA, nt_out, &gs->d_data, &gs->cap_data)) return rc;
+        if (int rc = gather_buf(gs, THZ_BUF_DATA, nt_out, &gs->d_data)) return rc;
     if (gather >= THZ_GATHER_ALL) {
-        if (int rc = gather_buf(gs, THZ_BUF_FFT, 2 * nf, &gs->d_fft, &gs->cap_fft)) return rc;
-        if (int rc = gather_buf(gs, THZ_BUF_AMPLITUDES, nf, &gs->d_amp, &gs->cap_amp)) return rc;
-        if (int rc = gather_buf(gs, THZ_BUF_PHASES, nf, &gs->d_ph, &gs->cap_ph)) return rc;
+        if (int rc = gather_buf(gs, THZ_BUF_FFT, 2 * nf, &gs->d_fft)) return rc;
+        if (int rc = gather_buf(gs, THZ_BUF_AMPLITUDES, nf, &gs->d_amp)) return rc;
+        if (int rc = gather_buf(gs, THZ_BUF_PHASES, nf, &gs->d_ph)) return rc;
     }
     gs->gathered = gather;
     return thz_group_sync(g);

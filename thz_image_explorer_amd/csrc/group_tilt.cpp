@@ -50,17 +50,10 @@ int thz_group_session_estimate_tilt(thz_group_session *gs, int which, int mode, 
         GHIP_TRY(g, hipSetDevice(g->m[i].ctx->device));
         if (int rc = bufs.alloc(i, &d_scr[i], kWords * sizeof(uint64_t), "thz_group_session_estimate_tilt: scratch allocation failed")) return rc;
     }
-    if (gs->root_local >= 0 && gs->cap_peak < npix) {
+    if (gs->root_local >= 0) {
         thz_ctx *ctx = g->m[(size_t)gs->root_local].ctx;
         GHIP_TRY(g, hipSetDevice(ctx->device));
-        if (gs->d_peak) {
-            GHIP_TRY(g, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(gs->d_peak);
-            gs->d_peak = nullptr;
-            gs->cap_peak = 0;
-        }
-        GHIP_TRY(g, hipMalloc((void **)&gs->d_peak, 3 * npix * sizeof(float)));
-        gs->cap_peak = npix;
+        if (int rc = gs->d_peak.grow(ctx, 3 * npix)) return gfail(g, rc, std::string("thz_group_session_estimate_tilt: ") + thz_last_error(ctx));
     }
     gs->peak_pix = 0;
     if (int rc = each_member(g, "slab arrival times: ", [&](size_t i) { return thz_session_peak_map(gs->sess[i], which, mode); })) return rc;
@@ -69,7 +62,7 @@ int thz_group_session_estimate_tilt(thz_group_session *gs, int which, int mode, 
     for (int b = 0; b < 3; ++b) {
         std::vector<const float *> send;
         for (thz_session *s : gs->sess) send.push_back(static_cast<const float *>(session_buffer_ro(s, bufs_of[b])));
-        if (int rc = thz_group_gather(g, send.data(), counts.data(), gs->d_peak ? gs->d_peak + (size_t)b * gs->cap_peak : nullptr)) return rc;
+        if (int rc = thz_group_gather(g, send.data(), counts.data(), gs->d_peak ? gs->d_peak + (size_t)b * gs->peak_stride() : nullptr)) return rc;
     }
     // rank 0: the same moments kernels and the same fit a single session runs.  Whatever happens here, rank 0 goes on
     // to the all-reduce — its code travels with the result, so that no rank waits for one that has left.
@@ -79,8 +72,8 @@ int thz_group_session_estimate_tilt(thz_group_session *gs, int which, int mode, 
         GHIP_TRY(g, hipSetDevice(ctx->device));
         double m[10];
         thz_tilt_fit fit{};
-        int rc = thz_arrival_plane_moments(ctx, nx, ny, c0.dx, c0.dy, c0.dt_ps, reinterpret_cast<const int32_t *>(gs->d_peak),
-                                           gs->d_peak + gs->cap_peak, gs->d_peak + 2 * gs->cap_peak, rel_threshold, m);
+        int rc = thz_arrival_plane_moments(ctx, nx, ny, c0.dx, c0.dy, c0.dt_ps, gs->d_peak.as<const int32_t>(),
+                                           gs->d_peak + gs->peak_stride(), gs->d_peak + 2 * gs->peak_stride(), rel_threshold, m);
         if (rc) gfail(g, rc, std::string("thz_group_session_estimate_tilt: ") + thz_last_error(ctx));
         else rc = thz_host_arrival_plane_fit(m, &fit);
         const double d[6] = {fit.tilt_x_deg, fit.tilt_y_deg, fit.slope_x_ps_per_mm, fit.slope_y_ps_per_mm, fit.t0_ps, fit.rms_ps};
@@ -114,8 +107,8 @@ void *thz_group_session_peak_result(thz_group_session *gs, int which)
     if (!gs || gs->root_local < 0 || !gs->peak_pix || !gs->d_peak) return nullptr;
     switch (which) {
     case THZ_BUF_PEAK_INDEX: return gs->d_peak;
-    case THZ_BUF_PEAK_OFFSET: return gs->d_peak + gs->cap_peak;
-    case THZ_BUF_PEAK_VALUE: return gs->d_peak + 2 * gs->cap_peak;
+    case THZ_BUF_PEAK_OFFSET: return gs->d_peak + gs->peak_stride();
+    case THZ_BUF_PEAK_VALUE: return gs->d_peak + 2 * gs->peak_stride();
     default: return nullptr;
     }
 }

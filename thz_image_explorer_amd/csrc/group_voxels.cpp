@@ -52,8 +52,7 @@ extern "C" int thz_group_session_voxels(thz_group_session *gs, const thz_voxel_c
     // a collective); 16 KiB and a few words per member.
     for (size_t i = 0; i < nl; ++i) {
         GHIP_TRY(g, hipSetDevice(g->m[i].ctx->device));
-        GHIP_TRY(g, hipMalloc((void **)&d_scr[i], scratch * sizeof(uint64_t)));
-        bufs.held[i].push_back(d_scr[i]);
+        if (int rc = bufs.alloc(i, &d_scr[i], scratch * sizeof(uint64_t), "thz_group_session_voxels: scratch allocation failed")) return rc;
         d_hist[i] = d_scr[i];
         d_cnt[i] = d_scr[i] + off_cnt;
         d_flag[i] = d_scr[i] + off_flag;
@@ -74,23 +73,10 @@ extern "C" int thz_group_session_voxels(thz_group_session *gs, const thz_voxel_c
             rcs[i] = gfail(g, THZ_ERR_INVALID, "thz_group_session_voxels: capacity without a buffer");
             continue;
         }
-        const size_t npix = s->nx_cur * s->ny_cur, n = npix * nt;
+        const size_t npix = s->nx_cur * s->ny_cur;
         GHIP_TRY(g, hipSetDevice(ctx->device));
-        if (s->opacity_floats != n) {
-            if (s->d_opacity) {
-                GHIP_TRY(g, hipStreamSynchronize(ctx->stream));
-                (void)hipFree(s->d_opacity);
-            }
-            s->d_opacity = nullptr;
-            s->opacity_floats = 0;
-            if (hipMalloc((void **)&s->d_opacity, (n ? n : 1) * sizeof(float)) != hipSuccess) {
-                s->d_opacity = nullptr;
-                rcs[i] = gfail(g, THZ_ERR_HIP, "thz_group_session_voxels: opacity allocation failed");
-                continue;
-            }
-            s->opacity_floats = n;
-        }
-        rcs[i] = thz_voxel_opacity(ctx, npix, nt, static_cast<const float *>(thz_session_buffer(s, THZ_BUF_DATA)), cfg, s->d_opacity);
+        rcs[i] = session_size_opacity(s);
+        if (!rcs[i]) rcs[i] = thz_voxel_opacity(ctx, npix, nt, static_cast<const float *>(thz_session_buffer(s, THZ_BUF_DATA)), cfg, s->d_opacity);
         if (rcs[i]) gfail(g, rcs[i], std::string("thz_group_session_voxels: ") + thz_last_error(ctx));
     }
     if (int rc = agree_or_return(rcs)) return rc;
@@ -107,7 +93,7 @@ extern "C" int thz_group_session_voxels(thz_group_session *gs, const thz_voxel_c
                     thz_session *s = gs->sess[i];
                     GHIP_TRY(g, hipSetDevice(ctx->device));
                     GHIP_TRY(g, hipMemsetAsync(d_hist[i], 0, kSelBins * sizeof(uint64_t), ctx->stream));
-                    if (int rc2 = thz_select_histogram(ctx, s->d_opacity, s->opacity_floats, level, prefix, d_hist[i]))
+                    if (int rc2 = thz_select_histogram(ctx, s->d_opacity, s->d_opacity.count(), level, prefix, d_hist[i]))
                         return gfail(g, rc2, std::string("thz_group_session_voxels: ") + thz_last_error(ctx));
                 }
                 if (int rc2 = thz_group_all_reduce_u64(g, d_hist.data(), kSelBins)) return rc2;

@@ -50,7 +50,7 @@ int thz_optical_maps(thz_ctx *ctx, size_t npix, size_t nf, const float *d_amp, c
         g.k1[b] = cfg->band_k1[b];
     }
     StageTimer t(ctx, THZ_STAGE_OPTICAL);
-    launch_optical_map(ctx->stream, npix, (int)nf, d_amp, d_phase, static_cast<const float *>(ctx->ws), g, d_thickness, d_n, d_alpha,
+    launch_optical_map(ctx->stream, npix, (int)nf, d_amp, d_phase, ctx->ws.as<const float>(), g, d_thickness, d_n, d_alpha,
                        d_kappa, d_wraps, d_slope);
     return check_launch(ctx);
 }

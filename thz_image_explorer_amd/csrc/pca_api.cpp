@@ -107,7 +107,7 @@ int thz_pca_gram(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t r
     // no mu: zeros — x - 0 is x, bit for bit
     std::vector<float> m(L, 0.0f);
     if (mu) std::memcpy(m.data(), mu, L * sizeof(float));
-    if (int rc = thz_memcpy_h2d(ctx, static_cast<unsigned char *>(ctx->ws) + pca_gram_mu_offset((int)L), m.data(), L * sizeof(float)))
+    if (int rc = thz_memcpy_h2d(ctx, ctx->ws.as<unsigned char>() + pca_gram_mu_offset((int)L), m.data(), L * sizeof(float)))
         return rc;
     {
         StageTimer t(ctx, THZ_STAGE_PCA);
@@ -134,7 +134,7 @@ int thz_pca_scores(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t
     if (int rc = thz_memcpy_h2d(ctx, ctx->ws, tab.data(), tab.size() * sizeof(float))) return rc;
     const PcaView v = view_of(npix, L, d_x, row_stride, col_step, nullptr);
     StageTimer t(ctx, THZ_STAGE_PCA);
-    launch_pca_scores(ctx->stream, v, static_cast<const float *>(ctx->ws), K, d_scores);
+    launch_pca_scores(ctx->stream, v, ctx->ws.as<const float>(), K, d_scores);
     return check_launch(ctx);
 }
 

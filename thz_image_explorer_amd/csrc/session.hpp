@@ -9,8 +9,8 @@
 // One region of interest of a session (thz_session_set_rois) and its pixel list for the grid of the last recompute
 struct SessionRoi {
     std::vector<uint64_t> poly;   // (x, y) pairs as the reference keeps them: pixels of the raw grid
-    uint32_t *d_list = nullptr;   // THIS slab's pixels inside, in the reference's visiting order (y outer, x inner;
-    size_t list_cap = 0;          //   mask position (x, y) samples pixel [shape0 - y - 1, x], math_tools.rs:640-651)
+    DevBuf<uint32_t> d_list;      // THIS slab's pixels inside, in the reference's visiting order (y outer, x inner;
+                                  //   mask position (x, y) samples pixel [shape0 - y - 1, x], math_tools.rs:640-651)
     uint32_t count = 0;           // ... how many
     uint32_t total = 0;           // pixels of the WHOLE grid inside (= count unless the session is a group's slab)
     size_t for_rows = 0, for_cols = 0, for_scale = 0, for_x0 = 0, for_grid_rows = 0;  // what the list was built for
@@ -36,8 +36,7 @@ struct MapPlane {
 };
 struct ResidentMaps {
     static constexpr int kMaxPlanes = 5;
-    float *d = nullptr;
-    size_t cap = 0;          // words allocated
+    DevBuf<float> d;         // grow-only
     bool resident = false;
     MapPlane plane[kMaxPlanes];
     // plane i of the layout of the last maps_begin, resident or not: what the call's launch writes
@@ -46,8 +45,7 @@ struct ResidentMaps {
     size_t entries(int i) const { return resident ? plane[i].entries : 0; }
 };
 // Marks the family absent, lays `planes` out one behind the other and makes sure of max(their words, min_words) words:
-// a block that is too small is freed — behind a synchronisation of the stream — and allocated anew (a failed
-// allocation leaves no block).
+// a block that is too small is replaced by a larger one (DevBuf::grow; a failed allocation leaves no block).
 int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> planes, size_t min_words = 0);
 // the call's closing synchronisation; the planes are resident when it has succeeded
 int maps_commit(thz_ctx *ctx, ResidentMaps *m);
@@ -61,17 +59,14 @@ struct thz_session {
     // grid of everything behind the scaling stage (math_tools.rs:242-310): nx / s, ny / s, dx * s, dy * s
     size_t nx_cur = 0, ny_cur = 0, scale = 1, out_pix = 0;
     float dx_cur = 1.0f, dy_cur = 1.0f;
-    float *d_scaled = nullptr;                 // block-averaged raw cube when scale > 1
-    size_t scaled_floats = 0;
+    DevBuf<float> d_scaled;                    // block-averaged raw cube when scale > 1
     std::vector<float> time, time_out;
     size_t nt_out = 0, nf_out = 0;
-    float *d_raw = nullptr, *d_fft = nullptr, *d_amp = nullptr, *d_ph = nullptr, *d_data = nullptr,
-          *d_img = nullptr, *d_avg = nullptr;  // d_avg: [2 nf | nf | nf]
-    float *d_vec = nullptr;                    // pre | mask | post multipliers (+ tilt scratch)
-    float *h_vec = nullptr;                    // pinned host image of d_vec: the multipliers go up in one asynchronous copy
-    size_t vec_floats = 0;
-    float *d_tilt = nullptr;                   // extended cube when tilt != 0 (kept while its size stays the same): built by
-    size_t tilt_floats = 0, ins_count = 0;     //   the staged path, or on demand behind a one-launch chain (session_extended_src)
+    DevBuf<float> d_raw, d_fft, d_amp, d_ph, d_data, d_img, d_avg;  // d_avg: [2 nf | nf | nf]
+    DevBuf<float> d_vec;                       // pre | mask | post multipliers (+ tilt scratch)
+    PinnedBuf<float> h_vec;                    // pinned host image of d_vec: the multipliers go up in one asynchronous copy
+    DevBuf<float> d_tilt;                      // extended cube when tilt != 0 (kept while its size stays the same): built by
+                                               //   the staged path, or on demand behind a one-launch chain (session_extended_src)
     std::vector<int32_t> ins_host;             // the insert indices d_ins holds (a recompute with the same plan does not copy them again)
     // a tilted chain that ran as ONE launch from the untilted cube (FBP plans, thz_pipeline_tilted): what the launch
     // gathered from, so that the extended traces can still be built for whoever needs them
@@ -82,25 +77,21 @@ struct thz_session {
     bool src_sum_own = false;                  // d_msum[0, nt_out) is THIS session's sum of source traces (a group adds the slabs')
     // ... the re-laid traces' sum depends on the source cube, the scale factor and the tilt only (src_gen): kept, like
     // d_rawsum, so that a recompute that moves another slider does not read the raw cube for it again
-    float *d_tiltsum = nullptr;
-    size_t tiltsum_floats = 0;
+    DevBuf<float> d_tiltsum;
     unsigned long tiltsum_gen = 0;             // the src_gen it belongs to, 0 = none
     std::vector<float> fd_real, fd_cmask;      // further Frequency-domain plugins: K14 real (nf), K13 complex (2 nf)
     thz_chain_cfg last_cfg{};                  // configuration of the last full recompute (decides whether a
     bool have_last_cfg = false;                // start position >= 6 may reuse the resident spectrum)
-    float *d_deconv = nullptr, *d_deconv_img = nullptr;  // output of the Deconvolution stage (thz_session_deconvolve)
-    size_t deconv_floats = 0;
+    DevBuf<float> d_deconv, d_deconv_img;      // output of the Deconvolution stage (thz_session_deconvolve)
     bool deconv_current = false;               // ... and whether it is the chain's final output right now
-    float *d_opacity = nullptr;                // voxel opacities of the final cube (thz_session_voxels)
-    size_t opacity_floats = 0;
-    int32_t *d_ins = nullptr;
+    DevBuf<float> d_opacity;                   // voxel opacities of the final cube (thz_session_voxels)
+    DevBuf<int32_t> d_ins;
     // the analysis maps of the last call of each family (ResidentMaps above): the planes are those of the family's
     // THZ_BUF_* ids, in their order (kMapIds in session_api.cpp)
     ResidentMaps maps[kMapFamilies];
     SessionCube sparse_cube;     // kMapSparse: the spike trains as a cube, on the grid, pitch and time step of the cube they were taken of
-    float *d_rawsum = nullptr;   // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
-    float *d_msum = nullptr;     // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
-    size_t msum_floats = 0;
+    DevBuf<float> d_rawsum;      // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
+    DevBuf<float> d_msum;        // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     bool msum_fast = false;      // the last recompute left its undivided sums in d_msum (want_means == 1)
     bool have_means = false;
     bool have_outputs = false;   // a recompute has run
@@ -123,18 +114,16 @@ struct thz_session {
     bool phases_known = false;
     unsigned long phase_gen = 0;     // the src_gen the knowledge belongs to
     std::vector<float> phase_pre;    // the pre-transform multiplier of the launch that wrote them
-    float *d_phsum = nullptr;        // (nf) that launch's in-launch sums of the phases, if it carried sums
-    size_t phsum_floats = 0;
+    DevBuf<float> d_phsum;           // (nf) that launch's in-launch sums of the phases, if it carried sums
     bool phsum_valid = false;
     const float *d_src = nullptr;  // what the fft stage read: d_raw, d_scaled or d_tilt (extended axis); null while a
                                    //   one-launch tilted chain's extended cube has not been asked for
     // ---- regions of interest (session_roi.cpp)
     std::vector<SessionRoi> rois;
-    float *d_roi_sum = nullptr;    // [amplitudes R x nf | phases R x nf | stage-input traces R x nt | final traces R x nt]:
-    float *d_roi = nullptr;        //   this session's (after a group's all-reduce: the grid's) sums, and the means
-    size_t roi_floats = 0;
-    float *d_wsep = nullptr;       // the three time multipliers in front of the transform, one by one (reference-order
-    size_t wsep_floats = 0;        //   roi_data): [tilt taper | Time Band Pass | fft window], nt_out each
+    DevBuf<float> d_roi_sum;       // [amplitudes R x nf | phases R x nf | stage-input traces R x nt | final traces R x nt]:
+    DevBuf<float> d_roi;           //   this session's (after a group's all-reduce: the grid's) sums, and the means
+    DevBuf<float> d_wsep;          // the three time multipliers in front of the transform, one by one (reference-order
+                                   //   roi_data): [tilt taper | Time Band Pass | fft window], nt_out each
     bool wsep_on[3] = {false, false, false};
     std::vector<float> roi_polar;  // avg_in_fourier_space: per region the polar inverse transform (nt_out each), host
     std::vector<char> roi_polar_ok;  //   0: realfft would have refused the spectrum (the reference falls back to the traces)
@@ -156,8 +145,7 @@ struct thz_session {
     size_t grid_x0 = 0, grid_rows = 0;
     // scaling over slab edges: the undivided partial sums of the block this slab only holds the first rows of (handed
     // to the next slab by the group), and the previous slab's for the block this one completes; (ny / s) x nt each
-    float *d_carry_out = nullptr, *d_carry_in = nullptr;
-    size_t carry_floats = 0;
+    DevBuf<float> d_carry_out, d_carry_in;
     bool carry_out_valid = false;
     bool msum_passes = false;    // a group's slab, tilted: d_msum = [unused nt | sum fft 2 nf | sum amplitudes nf | sum phases nf]
 };
@@ -210,10 +198,14 @@ int session_means(thz_session *s, const thz_chain_cfg *cfg, size_t total_pix);
 int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only);
 int session_roi_finish(thz_session *s, const thz_chain_cfg *cfg, bool data_only);
 size_t session_roi_floats(const thz_session *s);
-void session_roi_free(thz_session *s);
 // peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA, or THZ_BUF_SPARSE: the spike trains, on the grid
 // and time axis of the cube they were taken of) with its grid, trace length and the mean step of its time axis;
 // THZ_ERR_NOT_READY when it is absent
 int session_cube(thz_session *s, int which, SessionCube *out);
 // the ifft stage's avg_data (avg_in_fourier_space; needs the means): host-side, after session_means
 int session_avg_data(thz_session *s, const thz_chain_cfg *cfg);
+// The two buffers of a session that a group's stages size as well.  session_size_deconv: the Deconvolution stage's
+// outputs (d_deconv, d_deconv_img) for the current grid; a resize clears deconv_current.  session_size_opacity: the
+// opacity cube of the current grid.
+int session_size_deconv(thz_session *s);
+int session_size_opacity(thz_session *s);

@@ -15,32 +15,20 @@ namespace {
 float *final_data(const thz_session *s) { return s->deconv_current ? s->d_deconv : s->d_data; }
 float *final_img(const thz_session *s) { return s->deconv_current ? s->d_deconv_img : s->d_img; }
 
-template <class T>
-int dev_alloc(thz_ctx *ctx, T **p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    HIP_TRY(ctx, hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-    return THZ_OK;
-}
-
 int alloc_outputs(thz_session *s, size_t nt_out)
 {
     thz_ctx *ctx = s->ctx;
     const size_t npix = s->nx_cur * s->ny_cur, nf = nt_out / 2 + 1;
     if (nt_out == s->nt_out && npix == s->out_pix && s->d_fft) return THZ_OK;
     s->out_pix = 0;
-    if (int rc = dev_alloc(ctx, &s->d_fft, npix * nf * 2)) return rc;
-    if (int rc = dev_alloc(ctx, &s->d_amp, npix * nf)) return rc;
-    if (int rc = dev_alloc(ctx, &s->d_ph, npix * nf)) return rc;
-    if (int rc = dev_alloc(ctx, &s->d_data, npix * nt_out)) return rc;
-    if (int rc = dev_alloc(ctx, &s->d_avg, 4 * nf)) return rc;
-    s->vec_floats = 3 * nt_out + 3 * nf + 16;  // pre | post | mask | cmask (+ tilt scratch)
-    if (int rc = dev_alloc(ctx, &s->d_vec, s->vec_floats)) return rc;
-    if (s->h_vec) {
-        (void)hipHostFree(s->h_vec);
-        s->h_vec = nullptr;
-    }
-    HIP_TRY(ctx, hipHostMalloc((void **)&s->h_vec, s->vec_floats * sizeof(float), hipHostMallocDefault));
+    if (int rc = s->d_fft.exact(ctx, npix * nf * 2)) return rc;
+    if (int rc = s->d_amp.exact(ctx, npix * nf)) return rc;
+    if (int rc = s->d_ph.exact(ctx, npix * nf)) return rc;
+    if (int rc = s->d_data.exact(ctx, npix * nt_out)) return rc;
+    if (int rc = s->d_avg.exact(ctx, 4 * nf)) return rc;
+    const size_t vec_floats = 3 * nt_out + 3 * nf + 16;  // pre | post | mask | cmask (+ tilt scratch)
+    if (int rc = s->d_vec.exact(ctx, vec_floats)) return rc;
+    if (int rc = s->h_vec.exact(ctx, vec_floats)) return rc;
     s->nt_out = nt_out;
     s->nf_out = nf;
     s->out_pix = npix;
@@ -83,9 +71,9 @@ int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const floa
     s->nx_cur = nx; s->ny_cur = ny; s->dx_cur = dx; s->dy_cur = dy;
     s->time.assign(time, time + nt);
     s->time_out = s->time;
-    int rc = dev_alloc(ctx, &s->d_raw, nx * ny * nt);
-    if (!rc) rc = dev_alloc(ctx, &s->d_img, nx * ny);
-    if (!rc) rc = dev_alloc(ctx, &s->d_rawsum, nt);
+    int rc = s->d_raw.exact(ctx, nx * ny * nt);
+    if (!rc) rc = s->d_img.exact(ctx, nx * ny);
+    if (!rc) rc = s->d_rawsum.exact(ctx, nt);
     if (!rc) rc = alloc_outputs(s, nt);
     if (rc) { thz_session_destroy(s); return rc; }
     *out = s;
@@ -97,16 +85,7 @@ void thz_session_destroy(thz_session *s)
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    for (void *p : {(void *)s->d_raw, (void *)s->d_fft, (void *)s->d_amp, (void *)s->d_ph, (void *)s->d_data,
-                    (void *)s->d_img, (void *)s->d_avg, (void *)s->d_vec, (void *)s->d_tilt, (void *)s->d_ins,
-                    (void *)s->d_opacity, (void *)s->d_deconv, (void *)s->d_deconv_img, (void *)s->d_scaled,
-                    (void *)s->d_rawsum, (void *)s->d_msum, (void *)s->d_tiltsum, (void *)s->d_phsum, (void *)s->d_carry_in, (void *)s->d_carry_out})
-        if (p) (void)hipFree(p);
-    for (ResidentMaps &m : s->maps)
-        if (m.d) (void)hipFree(m.d);
-    if (s->h_vec) (void)hipHostFree(s->h_vec);
-    session_roi_free(s);
-    delete s;
+    delete s;  // every buffer is a member that frees itself
 }
 
 int thz_session_upload(thz_session *s, const float *cube, int subtract_bias)
@@ -228,12 +207,8 @@ int session_scale_tail(thz_session *s, const thz_chain_cfg *cfg)
     if (int rc = use_device(ctx)) return rc;
     const SlabScale sl = slab_scale(s->raw_grid_rows, s->slab_world, s->slab_rank, sf);
     const size_t need = (s->ny / sf) * s->nt;
-    if (s->carry_floats != need) {
-        s->carry_floats = 0;
-        if (int rc = dev_alloc(ctx, &s->d_carry_out, need)) return rc;
-        if (int rc = dev_alloc(ctx, &s->d_carry_in, need)) return rc;
-        s->carry_floats = need;
-    }
+    if (int rc = s->d_carry_out.exact(ctx, need)) return rc;
+    if (int rc = s->d_carry_in.exact(ctx, need)) return rc;
     if (sl.tail) {
         const float *rows = s->d_raw + (sl.head + sl.full * sf) * s->ny * s->nt;
         launch_scale_rows_partial(ctx->stream, rows, sl.tail, s->ny, s->nt, sf, nullptr, 0.0f, s->d_carry_out);
@@ -316,11 +291,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     s->dx_cur = dx_c; s->dy_cur = dy_c;
     const size_t npix = s->nx_cur * s->ny_cur;
     if (sf > 1) {
-        if (s->scaled_floats != npix * s->nt) {
-            s->scaled_floats = 0;
-            if (int rc = dev_alloc(ctx, &s->d_scaled, npix * s->nt)) return rc;
-            s->scaled_floats = npix * s->nt;
-        }
+        if (int rc = s->d_scaled.exact(ctx, npix * s->nt)) return rc;
         if (slab) {
             // the block the previous slab started: its partial sums (d_carry_in, put there by the group) + this slab's
             // leading rows, divided; then the blocks wholly inside.  Same adds in the same order as one session's.
@@ -356,11 +327,9 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
                 tilt_plan(time.data(), nt_cur, s->nx_cur, s->ny_cur, cfg->tilt_x_deg, cfg->tilt_y_deg, s->dx_cur, s->dy_cur,
                           new_time.data(), ins.data());
             }
-            if (s->ins_count != npix) {
-                s->ins_count = 0;
+            if (!s->d_ins.holds(npix)) {
                 s->ins_host.clear();
-                if (int rc = dev_alloc(ctx, &s->d_ins, npix)) return rc;
-                s->ins_count = npix;
+                if (int rc = s->d_ins.exact(ctx, npix)) return rc;
             }
             if (int rc = alloc_outputs(s, nt2)) return rc;
             if (s->ins_host != ins) {  // (kept by the session: the copy below may still read it when this block ends)
@@ -404,11 +373,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     if (want_sep) {
         std::memcpy(sep.data() + 2 * nt_cur, w.data(), nt_cur * sizeof(float));
         s->wsep_on[2] = true;
-        if (s->wsep_floats != 3 * nt_cur) {
-            s->wsep_floats = 0;
-            if (int rc = dev_alloc(ctx, &s->d_wsep, 3 * nt_cur)) return rc;
-            s->wsep_floats = 3 * nt_cur;
-        }
+        if (int rc = s->d_wsep.exact(ctx, 3 * nt_cur)) return rc;
         if (int rc = thz_memcpy_h2d(ctx, s->d_wsep, sep.data(), sep.size() * sizeof(float))) return rc;
     }
     int64_t band_lo = 0, band_hi = 0;  // [lower, upper) of the Frequency Band Pass: zero outside (band_pass_fd.rs:194-212)
@@ -450,11 +415,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     const bool fused_tilt = tilted && ctx->plan_d.family == kFamilyFBP;
     const float *tilt_from = src;
     if (tilted && !fused_tilt) {
-        if (s->tilt_floats != npix * nt_cur) {
-            s->tilt_floats = 0;
-            if (int rc = dev_alloc(ctx, &s->d_tilt, npix * nt_cur)) return rc;
-            s->tilt_floats = npix * nt_cur;
-        }
+        if (int rc = s->d_tilt.exact(ctx, npix * nt_cur)) return rc;
         launch_tilt(ctx->stream, npix, (int)tilt_nt_in, (int)nt_cur, src, d_taper, s->d_ins, s->d_tilt);
         if (int rc = check_launch(ctx)) return rc;
         src = s->d_tilt;
@@ -469,13 +430,8 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // a group's slab of a tilted cube on the staged path: sums that add up over the slabs — three passes over the
     // outputs, any order
     s->msum_passes = cfg->want_means == 1 && tilted && !fused_tilt && slab;
-    if (s->msum_fast || s->msum_passes) {
-        if (s->msum_floats != nt_cur + 4 * nf) {
-            s->msum_floats = 0;
-            if (int rc = dev_alloc(ctx, &s->d_msum, nt_cur + 4 * nf)) return rc;
-            s->msum_floats = nt_cur + 4 * nf;
-        }
-    }
+    if (s->msum_fast || s->msum_passes)
+        if (int rc = s->d_msum.exact(ctx, nt_cur + 4 * nf)) return rc;
     if (s->msum_fast && !fused_tilt) {
         // Σ of the source traces: cached at upload for the raw cube, one small pass for a block-averaged one
         // (the re-laid traces' comes out of thz_pipeline_tilted)
@@ -515,7 +471,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     // phases") — what a drag on the Frequency Band Pass, a plugin or the post Time Band Pass comes to.  A launch that
     // carries the sums then needs the kept phase sums.  THZ_F_KEEP_ZEROS=0 keeps its meaning;
     // THZ_F_KEEP_PHASES=0: developer knob, every launch computes and writes the phases.
-    const bool phsum_kept = s->phsum_valid && s->phsum_floats == nf;
+    const bool phsum_kept = s->phsum_valid && s->d_phsum.holds(nf);
     bool keep_phases = phases_before && !keep.all && !tilted && s->d_ph == ph_before && s->out_pix == pix_before && s->nt_out == nt_before
                        && s->phase_pre.size() == nt_cur && std::memcmp(s->phase_pre.data(), pre.data(), nt_cur * sizeof(float)) == 0
                        && (!s->msum_fast || phsum_kept);
@@ -525,15 +481,13 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
         io.d_raw = nullptr;
         thz_tilt_src ts{};
         ts.d_src = tilt_from; ts.nt_in = tilt_nt_in; ts.d_taper = d_taper; ts.d_insert_index = s->d_ins;
-        const bool sum_kept = s->msum_fast && s->tiltsum_gen == s->src_gen && s->tiltsum_floats == nt_cur;
+        const bool sum_kept = s->msum_fast && s->tiltsum_gen == s->src_gen && s->d_tiltsum.holds(nt_cur);
         ts.d_src_sum = s->msum_fast && !sum_kept ? s->d_msum : nullptr;
         if (int rc = pipeline_tilted_band(ctx, npix, &io, &ts, band_known ? (size_t)band_lo : 0, band_known ? (size_t)band_hi : 0, &keep)) return rc;
         if (s->msum_fast) {  // (session_means scales d_msum in place and a group all-reduces it: the kept copy is apart)
-            if (!sum_kept && s->tiltsum_floats != nt_cur) {
-                s->tiltsum_floats = 0;
+            if (!s->d_tiltsum.holds(nt_cur)) {
                 s->tiltsum_gen = 0;
-                if (int rc = dev_alloc(ctx, &s->d_tiltsum, nt_cur)) return rc;
-                s->tiltsum_floats = nt_cur;
+                if (int rc = s->d_tiltsum.exact(ctx, nt_cur)) return rc;
             }
             HIP_TRY(ctx, hipMemcpyAsync(sum_kept ? s->d_msum : s->d_tiltsum, sum_kept ? s->d_tiltsum : s->d_msum, nt_cur * sizeof(float),
                                         hipMemcpyDeviceToDevice, ctx->stream));
@@ -554,11 +508,7 @@ int session_enqueue(thz_session *s, const thz_chain_cfg *cfg, int start_stage, b
     } else if (keep.honoured && !tilted) {  // (a launch of a family that was not told leaves nothing known)
         s->phsum_valid = false;
         if (s->msum_fast) {
-            if (s->phsum_floats != nf) {
-                s->phsum_floats = 0;
-                if (int rc = dev_alloc(ctx, &s->d_phsum, nf)) return rc;
-                s->phsum_floats = nf;
-            }
+            if (int rc = s->d_phsum.exact(ctx, nf)) return rc;
             HIP_TRY(ctx, hipMemcpyAsync(s->d_phsum, s->d_msum + nt_cur + nf, nf * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
             s->phsum_valid = true;
         }
@@ -592,11 +542,7 @@ int session_extended_src(thz_session *s)
     if (!s->tilt_fused || s->d_src) return THZ_OK;
     thz_ctx *ctx = s->ctx;
     const size_t npix = s->nx_cur * s->ny_cur, nt = s->nt_out;
-    if (s->tilt_floats != npix * nt) {
-        s->tilt_floats = 0;
-        if (int rc = dev_alloc(ctx, &s->d_tilt, npix * nt)) return rc;
-        s->tilt_floats = npix * nt;
-    }
+    if (int rc = s->d_tilt.exact(ctx, npix * nt)) return rc;
     {
         StageTimer t(ctx, THZ_STAGE_TD_WINDOW);
         launch_tilt(ctx->stream, npix, (int)s->tilt_nt_in, (int)nt, s->tilt_from, s->d_taper, s->d_ins, s->d_tilt);
@@ -675,6 +621,16 @@ int thz_session_set_fd_filters(thz_session *s, const float *real_mask, const flo
 
 }  // extern "C"
 
+int session_size_deconv(thz_session *s)
+{
+    const size_t npix = s->nx_cur * s->ny_cur, n = npix * s->nt_out;
+    if (!s->d_deconv.holds(n) || !s->d_deconv_img.holds(npix)) s->deconv_current = false;
+    if (int rc = s->d_deconv.exact(s->ctx, n)) return rc;
+    return s->d_deconv_img.exact(s->ctx, npix);
+}
+
+int session_size_opacity(thz_session *s) { return s->d_opacity.exact(s->ctx, s->nx_cur * s->ny_cur * s->nt_out); }
+
 extern "C" {
 
 int thz_session_deconvolve(thz_session *s, const thz_psf *psf, const thz_deconv_cfg *cfg,
@@ -684,14 +640,7 @@ int thz_session_deconvolve(thz_session *s, const thz_psf *psf, const thz_deconv_
     thz_ctx *ctx = s->ctx;
     if (!s->have_outputs) return fail(ctx, THZ_ERR_NOT_READY, "thz_session_deconvolve: no recompute has run");
     if (int rc = use_device(ctx)) return rc;
-    const size_t npix = s->nx_cur * s->ny_cur, n = npix * s->nt_out;
-    if (s->deconv_floats != n) {
-        s->deconv_floats = 0;
-        s->deconv_current = false;
-        if (int rc = dev_alloc(ctx, &s->d_deconv, n)) return rc;
-        if (int rc = dev_alloc(ctx, &s->d_deconv_img, npix)) return rc;
-        s->deconv_floats = n;
-    }
+    if (int rc = session_size_deconv(s)) return rc;
     // the engine's axis is the chain's current one unless a plot call re-planned in between
     if (ctx->time.size() != s->nt_out)
         if (int rc = thz_set_time_axis(ctx, s->time_out.data(), s->nt_out)) return rc;
@@ -757,16 +706,7 @@ int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> pl
         m->plane[i++] = p;
     }
     for (; i < ResidentMaps::kMaxPlanes; ++i) m->plane[i] = MapPlane{};
-    need = std::max(need, min_words);
-    if (need > m->cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (m->d) (void)hipFree(m->d);
-        m->d = nullptr;
-        m->cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&m->d, need * sizeof(float)));
-        m->cap = need;
-    }
-    return THZ_OK;
+    return m->d.grow(ctx, std::max(need, min_words));
 }
 
 int maps_commit(thz_ctx *ctx, ResidentMaps *m)
@@ -821,7 +761,7 @@ const void *session_buffer_ro(thz_session *s, int which)
     case THZ_BUF_AVG_FFT: return s->have_means ? s->d_avg : nullptr;
     case THZ_BUF_AVG_AMPLITUDES: return s->have_means ? s->d_avg + 2 * nf : nullptr;
     case THZ_BUF_AVG_PHASES: return s->have_means ? s->d_avg + 3 * nf : nullptr;
-    case THZ_BUF_OPACITY: return s->opacity_floats == s->nx_cur * s->ny_cur * s->nt_out ? s->d_opacity : nullptr;
+    case THZ_BUF_OPACITY: return s->d_opacity.holds(s->nx_cur * s->ny_cur * s->nt_out) ? s->d_opacity : nullptr;
     default: return nullptr;
     }
 }
@@ -870,29 +810,21 @@ int thz_session_voxels(thz_session *s, const thz_voxel_cfg *cfg, uint64_t max_in
     if (capacity && !host_out) return fail(ctx, THZ_ERR_INVALID, "thz_session_voxels: capacity without a buffer");
     if (int rc = use_device(ctx)) return rc;
     const size_t npix = s->nx_cur * s->ny_cur, nt = s->nt_out, n = npix * nt;
-    if (s->opacity_floats != n) {
-        s->opacity_floats = 0;
-        if (int rc = dev_alloc(ctx, &s->d_opacity, n)) return rc;
-        s->opacity_floats = n;
-    }
+    if (int rc = session_size_opacity(s)) return rc;
     if (int rc = thz_voxel_opacity(ctx, npix, nt, final_data(s), cfg, s->d_opacity)) return rc;
     float thr = 0.0f;
     if (int rc = thz_voxel_threshold(ctx, s->d_opacity, n, max_instances, &thr)) return rc;
     if (threshold) *threshold = thr;
     const float time_span = s->time_out.back() - s->time_out.front();
-    thz_voxel_instance *d_inst = nullptr;
-    if (capacity) HIP_TRY(ctx, hipMalloc((void **)&d_inst, capacity * sizeof(thz_voxel_instance)));
-    int rc = thz_voxel_instances(ctx, s->d_opacity, s->nx_cur, s->ny_cur, nt, 0, s->nx_cur, thr, time_span, scaling, orig_w, orig_h,
-                                 orig_d, d_inst, capacity, count, cube_dims);
-    if (!rc && capacity) {
-        const uint64_t n_copy = *count < capacity ? *count : capacity;
-        if (n_copy) rc = thz_memcpy_d2h(ctx, host_out, d_inst, n_copy * sizeof(thz_voxel_instance));
-    }
-    if (d_inst) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_inst);
-    }
-    return rc;
+    CallBuf<thz_voxel_instance> d_inst(ctx);
+    if (capacity)
+        if (int rc = d_inst.alloc(capacity)) return rc;
+    if (int rc = thz_voxel_instances(ctx, s->d_opacity, s->nx_cur, s->ny_cur, nt, 0, s->nx_cur, thr, time_span, scaling, orig_w, orig_h,
+                                     orig_d, d_inst, capacity, count, cube_dims))
+        return rc;
+    const uint64_t n_copy = *count < capacity ? *count : capacity;
+    if (n_copy) return thz_memcpy_d2h(ctx, host_out, d_inst, n_copy * sizeof(thz_voxel_instance));
+    return THZ_OK;
 }
 
 int thz_session_plot(thz_session *s, size_t px, size_t py, const thz_plot_out *out)
@@ -932,35 +864,34 @@ int thz_session_plot(thz_session *s, size_t px, size_t py, const thz_plot_out *o
         if (int rc = thz_session_download(s, THZ_BUF_AVG_PHASES, 0, 1, out->avg_phase_fft)) return rc;
     if (out->signal_fft || out->phase_fft || out->avg_signal) {
         // scratch behind the multipliers: [amp nf | phase nf | mean nt | this pixel's re-laid trace nt]
-        float *d_tmp = nullptr;
-        HIP_TRY(ctx, hipMalloc((void **)&d_tmp, (2 * nf + 2 * nt) * sizeof(float)));
-        int rc = THZ_OK;
+        CallBuf<float> d_tmp(ctx);
+        if (int rc = d_tmp.alloc(2 * nf + 2 * nt)) return rc;
         if (out->signal_fft || out->phase_fft) {
             // the fft stage's own amplitudes / phases (no band-pass yet): one trace through K1-K3 again
-            if (ctx->time.size() != nt) rc = thz_set_time_axis(ctx, s->time_out.data(), nt);
+            if (ctx->time.size() != nt)
+                if (int rc = thz_set_time_axis(ctx, s->time_out.data(), nt)) return rc;
             const float *src = s->d_src ? s->d_src + pix * nt : nullptr;
             if (!src) {  // a one-launch tilted chain left no extended cube: this pixel's trace alone
                 float *one = d_tmp + 2 * nf + nt;
                 launch_tilt(ctx->stream, 1, (int)s->tilt_nt_in, (int)nt, s->tilt_from + pix * s->tilt_nt_in, s->d_taper,
                             s->d_ins + pix, one);
-                if (!rc) rc = check_launch(ctx);
+                if (int rc = check_launch(ctx)) return rc;
                 src = one;
             }
-            if (!rc) rc = thz_fft(ctx, 1, src, s->d_vec /* pre */, nullptr, nullptr, nullptr, d_tmp, d_tmp + nf, nullptr);
-            if (!rc && out->signal_fft) rc = thz_memcpy_d2h(ctx, out->signal_fft, d_tmp, nf * sizeof(float));
-            if (!rc && out->phase_fft) rc = thz_memcpy_d2h(ctx, out->phase_fft, d_tmp + nf, nf * sizeof(float));
+            if (int rc = thz_fft(ctx, 1, src, s->d_vec /* pre */, nullptr, nullptr, nullptr, d_tmp, d_tmp + nf, nullptr)) return rc;
+            if (out->signal_fft)
+                if (int rc = thz_memcpy_d2h(ctx, out->signal_fft, d_tmp, nf * sizeof(float))) return rc;
+            if (out->phase_fft)
+                if (int rc = thz_memcpy_d2h(ctx, out->phase_fft, d_tmp + nf, nf * sizeof(float))) return rc;
         }
-        if (!rc && out->avg_signal) {
+        if (out->avg_signal) {
             if (s->have_last_cfg && s->last_cfg.avg_in_fourier_space && s->avg_data.size() == nt) {
                 std::memcpy(out->avg_signal, s->avg_data.data(), nt * sizeof(float));  // filtered.avg_data, data_thread.rs:1431
             } else {
-                rc = thz_pixel_mean(ctx, s->nx_cur, s->ny_cur, nt, 1, final_data(s), d_tmp + 2 * nf);
-                if (!rc) rc = thz_memcpy_d2h(ctx, out->avg_signal, d_tmp + 2 * nf, nt * sizeof(float));
+                if (int rc = thz_pixel_mean(ctx, s->nx_cur, s->ny_cur, nt, 1, final_data(s), d_tmp + 2 * nf)) return rc;
+                if (int rc = thz_memcpy_d2h(ctx, out->avg_signal, d_tmp + 2 * nf, nt * sizeof(float))) return rc;
             }
         }
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_tmp);
-        if (rc) return rc;
     }
     return THZ_OK;
 }

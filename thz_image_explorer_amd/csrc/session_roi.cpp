@@ -42,22 +42,19 @@ int build_lists(thz_session *s)
     thz_ctx *ctx = s->ctx;
     const size_t rows = s->nx_cur, cols = s->ny_cur;
     const size_t grid_rows = s->grid_rows ? s->grid_rows : rows, x0 = s->grid_rows ? s->grid_x0 : 0;
-    uint8_t *d_mask = nullptr;
+    CallBuf<uint8_t> d_mask(ctx);
     std::vector<uint8_t> mask;
     std::vector<uint32_t> list;
-    int rc = THZ_OK;
     for (SessionRoi &r : s->rois) {
         if (r.for_rows == rows && r.for_cols == cols && r.for_scale == s->scale && r.for_x0 == x0 && r.for_grid_rows == grid_rows)
             continue;
         if (!d_mask) {
-            HIP_TRY(ctx, hipMalloc((void **)&d_mask, grid_rows * cols));
+            if (int rc = d_mask.alloc(grid_rows * cols)) return rc;
             mask.resize(grid_rows * cols);
         }
         // the whole grid's mask: the bounding box is clamped to the whole array's bounds (math_tools.rs:632-637)
-        rc = thz_roi_mask(ctx, r.poly.data(), r.poly.size() / 2, (uint64_t)s->scale, grid_rows, cols, d_mask);
-        if (rc) break;
-        rc = thz_memcpy_d2h(ctx, mask.data(), d_mask, mask.size());
-        if (rc) break;
+        if (int rc = thz_roi_mask(ctx, r.poly.data(), r.poly.size() / 2, (uint64_t)s->scale, grid_rows, cols, d_mask)) return rc;
+        if (int rc = thz_memcpy_d2h(ctx, mask.data(), d_mask, mask.size())) return rc;
         list.clear();
         uint32_t total = 0;
         for (size_t y = 0; y < grid_rows; ++y)
@@ -67,55 +64,20 @@ int build_lists(thz_session *s)
                     const size_t row = grid_rows - y - 1;  // :647
                     if (row >= x0 && row < x0 + rows) list.push_back((uint32_t)((row - x0) * cols + x));
                 }
-        if (list.size() > r.list_cap) {
-            if (r.d_list) (void)hipFree(r.d_list);
-            r.d_list = nullptr;
-            r.list_cap = 0;
-            if (hipMalloc((void **)&r.d_list, list.size() * sizeof(uint32_t)) != hipSuccess) {
-                rc = fail(ctx, THZ_ERR_HIP, "region of interest: allocation of the pixel list failed");
-                break;
-            }
-            r.list_cap = list.size();
-        }
-        if (!list.empty()) {
-            rc = thz_memcpy_h2d(ctx, r.d_list, list.data(), list.size() * sizeof(uint32_t));
-            if (rc) break;
-        }
+        if (int rc = r.d_list.grow(ctx, list.size())) return rc;
+        if (!list.empty())
+            if (int rc = thz_memcpy_h2d(ctx, r.d_list, list.data(), list.size() * sizeof(uint32_t))) return rc;
         r.count = (uint32_t)list.size();
         r.total = total;
         ++s->src_gen;  // other pixels: the kept sums of the source traces are void
         r.for_rows = rows; r.for_cols = cols; r.for_scale = s->scale; r.for_x0 = x0; r.for_grid_rows = grid_rows;
     }
-    if (d_mask) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_mask);
-    }
-    return rc;
-}
-
-template <class T>
-int dev_realloc(thz_ctx *ctx, T **p, size_t n)
-{
-    if (*p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(*p); *p = nullptr; }
-    HIP_TRY(ctx, hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
     return THZ_OK;
 }
 
 }  // namespace
 
 size_t session_roi_floats(const thz_session *s) { return layout(s).total(); }
-
-void session_roi_free(thz_session *s)
-{
-    for (SessionRoi &r : s->rois)
-        if (r.d_list) (void)hipFree(r.d_list);
-    s->rois.clear();
-    for (void *p : {(void *)s->d_roi, (void *)s->d_roi_sum, (void *)s->d_wsep})
-        if (p) (void)hipFree(p);
-    s->d_roi = s->d_roi_sum = s->d_wsep = nullptr;
-    s->roi_floats = s->wsep_floats = 0;
-    s->have_rois = false;
-}
 
 int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only_io)
 {
@@ -126,13 +88,11 @@ int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only_i
     if (int rc = use_device(ctx)) return rc;
     if (int rc = build_lists(s)) return rc;
     const RoiLayout L = layout(s);
-    if (s->roi_floats != L.total()) {
-        s->roi_floats = 0;
-        if (int rc = dev_realloc(ctx, &s->d_roi, L.total())) return rc;
-        if (int rc = dev_realloc(ctx, &s->d_roi_sum, L.total())) return rc;
-        s->roi_floats = L.total();
+    if (!s->d_roi.holds(L.total()) || !s->d_roi_sum.holds(L.total())) {
         s->roi_src_gen = 0;
         data_only = false;  // nothing to keep
+        if (int rc = s->d_roi.exact(ctx, L.total())) return rc;
+        if (int rc = s->d_roi_sum.exact(ctx, L.total())) return rc;
     }
     *data_only_io = data_only;
     const bool ordered = cfg->want_means == 2;
@@ -186,7 +146,7 @@ int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only_i
 int session_roi_finish(thz_session *s, const thz_chain_cfg *cfg, bool data_only)
 {
     thz_ctx *ctx = s->ctx;
-    if (s->rois.empty() || !s->have_outputs || s->roi_floats == 0) return THZ_OK;
+    if (s->rois.empty() || !s->have_outputs || !s->d_roi_sum) return THZ_OK;
     if (int rc = use_device(ctx)) return rc;
     const RoiLayout L = layout(s);
     const bool ordered = cfg->want_means == 2;
@@ -264,11 +224,10 @@ int thz_session_set_rois(thz_session *s, size_t n_rois, const size_t *n_vertices
     thz_ctx *ctx = s->ctx;
     if (int rc = use_device(ctx)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (SessionRoi &r : s->rois)
-        if (r.d_list) (void)hipFree(r.d_list);
     s->rois.clear();
     s->have_rois = false;
-    s->roi_floats = 0;  // the next recompute takes every sum afresh, whatever its start position
+    s->d_roi.drop(ctx);  // the next recompute takes every sum afresh, whatever its start position
+    s->d_roi_sum.drop(ctx);
     size_t off = 0;
     for (size_t i = 0; i < n_rois; ++i) {
         SessionRoi r;

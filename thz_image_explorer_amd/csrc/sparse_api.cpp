@@ -26,7 +26,7 @@ int thz_sparse_deconv(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data,
     if (int rc = ensure_ws(ctx, table.size() * sizeof(float))) return rc;
     if (int rc = thz_memcpy_h2d(ctx, ctx->ws, table.data(), table.size() * sizeof(float))) return rc;
     StageTimer t(ctx, THZ_STAGE_ECHO);
-    const hipError_t e = launch_sparse_deconv(ctx->stream, npix, g, d_data, static_cast<const float *>(ctx->ws), d_out, d_resid, d_nnz);
+    const hipError_t e = launch_sparse_deconv(ctx->stream, npix, g, d_data, ctx->ws.as<const float>(), d_out, d_resid, d_nnz);
     if (e != hipSuccess) return fail(ctx, THZ_ERR_HIP, std::string("thz_sparse_deconv: ") + hipGetErrorString(e));
     return THZ_OK;
 }

@@ -32,7 +32,7 @@ int voxel_ws(thz_ctx *ctx, size_t npix, VoxelWs *w)
     const size_t off_tiles = off_offsets + npix * sizeof(uint64_t);
     const size_t off_total = off_tiles + ntiles * sizeof(uint64_t);
     if (int rc = ensure_ws(ctx, off_total + sizeof(uint64_t))) return rc;
-    char *ws = static_cast<char *>(ctx->ws);
+    char *ws = ctx->ws.as<char>();
     w->counts = reinterpret_cast<uint32_t *>(ws);
     w->offsets = reinterpret_cast<unsigned long long *>(ws + off_offsets);
     w->tiles = reinterpret_cast<unsigned long long *>(ws + off_tiles);
@@ -134,7 +134,7 @@ int thz_voxel_opacity(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data,
         if (int rc = ensure_ws(ctx, k.size() * sizeof(float))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // k dies at return
-        d_wide = static_cast<const float *>(ctx->ws);
+        d_wide = ctx->ws.as<const float>();
     }
     StageTimer t(ctx, THZ_STAGE_VOXEL_OPACITY);
     if (!launch_voxel_opacity(ctx->stream, npix, (int)nt, d_data, taps, d_wide, r, cfg->contrast,
@@ -174,7 +174,7 @@ int thz_kth_largest(thz_ctx *ctx, const float *d_vals, size_t n, uint64_t k, flo
     if (!d_vals || !out || k < 1 || k > n) return fail(ctx, THZ_ERR_INVALID, "thz_kth_largest: need 1 <= k <= n");
     if (int rc = use_device(ctx)) return rc;
     if (int rc = ensure_ws(ctx, kSelBins * sizeof(uint64_t))) return rc;
-    uint64_t *d_hist = static_cast<uint64_t *>(ctx->ws);
+    uint64_t *d_hist = ctx->ws.as<uint64_t>();
     StageTimer t(ctx, THZ_STAGE_VOXEL_SELECT);
     bool too_few = false;
     const int rc = select_walk(
