@@ -695,6 +695,62 @@ int thz_host_sparse_trace(const float *y, size_t nt, const float *taps, const th
                           float *x, float *resid, int32_t *nnz);
 int thz_host_sparse_kernel(const float *ref, size_t nref, int n_taps, int center, float *taps, float *step);
 
+/* ------------------------------------------------------------------ */
+/* Unmixing every pixel into its materials: NNLS (K22) */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  "How much of each material is in every pixel?": for a pixel's row x and K known spectra
+ * (the endmembers E, K x L — from a library, from pixels picked by hand, or the k-means centroids) the abundances a
+ * minimise |x - E^T a|^2 subject to a >= 0.  All device arithmetic is f32.
+ *
+ * thz_unmix sees the matrix of the PCA calls above — X[p, j] = d_x[p * row_stride + j * col_step], 1 <= L <=
+ * THZ_PCA_MAX_LEN, col_step >= 1, 4-byte alignment only — and K x L host floats `endmembers`, 1 <= K <= THZ_UNMIX_MAX
+ * (= THZ_CLUSTER_MAX: centroids feed it directly), which go up once per call.
+ *   element      u[p, j] = X[p, j] when cfg->absorbance == 0; otherwise u = lref[j] - logf(X[p, j]) (ONE f32
+ *                subtraction) with lref[j] = (float)log((double)ref[j]) made on the host: Beer-Lambert absorbance against
+ *                the reference spectrum `ref` of L host floats, required, finite and > 0 when absorbance != 0 (not read
+ *                otherwise).  The endmembers are then absorbance spectra too.
+ *   projection   b[c] = sum_j u[p, j] E[c, j], one wave per pixel: lane l adds j = l, l + 64, ... in ascending order,
+ *                acc = fmaf(u, E, acc), then the lanes as the fixed tree of thz_pca_scores — the order depends on L
+ *                alone, and |b - exact| <= (ceil(L / 64) + 8) 2^-24 sum_j |u E|, exact the f64 sum over the f32 u.
+ *                With absorbance u itself lies within 2 ulp of |log X| plus one rounding of the subtraction of the f64
+ *                value (DESIGN.md §4.12 has what was measured).
+ *   normal matrix  on the host, thz_host_unmix_prepare, plain C++ with no GPU and no context: G64[i][c] = sum_j
+ *                (double)E[i, j] (double)E[c, j] with j ascending, G = (float)G64, rd[c] = (float)(1.0 / G64[c][c]).
+ *                THZ_ERR_INVALID for a non-finite entry, a zero endmember (G64[c][c] == 0), a non-finite rd, K outside
+ *                1 .. THZ_UNMIX_MAX, L outside 1 .. THZ_PCA_MAX_LEN or a NULL pointer.
+ *   solve        cyclic coordinate descent on the normal equations, one pixel at a time, from b, G, rd alone:
+ *                    a[c] = +0, g[c] = -b[c]
+ *                    sweep s = 0 .. n_sweeps-1, c = 0 .. K-1 in order:
+ *                        an = fmaxf(fmaf(-g[c], rd[c], a[c]), 0.0f);  d = an - a[c];
+ *                        for i = 0 .. K-1: g[i] = fmaf(G[i][c], d, g[i]);   a[c] = an;
+ *                    kkt = max over c of (a[c] > 0 ? fabsf(g[c]) : fmaxf(-g[c], 0))
+ *                g is the running gradient, not recomputed.  n_sweeps in 0 .. THZ_UNMIX_MAX_SWEEPS.  The update for
+ *                d == 0 may be skipped, and a pixel (or a whole wave) whose last full sweep changed nothing may stop:
+ *                the remaining sweeps would repeat it.  thz_host_unmix_solve is the plain-C++ twin: for finite data
+ *                it equals the device bit for bit from the device's own b, -0 and +0 compared as numbers.
+ *   residual     resid[p] = sum_j (u[p, j] - m_j)^2 with m_j the fmaf(a[c], E[c, j], m) chain from +0 over ascending c,
+ *                the squares summed in any order; computed directly in a second pass over the row, never as
+ *                xx - 2 a.b + a G a, which cancels.
+ * d_abund (K, npix), endmember-major, is required; d_proj (K, npix) takes the b's; d_resid and d_kkt are (npix).  Each of
+ * d_proj, d_resid and d_kkt may be NULL, and the second read of the cube is skipped when d_resid is NULL.
+ * A row with a non-finite element has unspecified values in its own outputs and affects no other pixel.  npix == 0 is a
+ * no-op.  Anything outside these limits, or a NULL required pointer, is THZ_ERR_INVALID before any launch or
+ * allocation.  No floating-point atomics: the same inputs give the same bits on every run.  Time of the three launches
+ * under THZ_STAGE_PCA. */
+#define THZ_UNMIX_MAX 16
+#define THZ_UNMIX_MAX_SWEEPS 4096
+typedef struct thz_unmix_cfg {
+    int32_t n_endmembers;        /* K, 1 .. THZ_UNMIX_MAX */
+    int32_t n_sweeps;            /* 0 .. THZ_UNMIX_MAX_SWEEPS */
+    int32_t absorbance;          /* 0: u = X; otherwise u = log(ref) - log(X) */
+} thz_unmix_cfg;
+int thz_unmix(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_stride, size_t col_step,
+              const float *endmembers /* K x L host */, const float *ref /* L host, or NULL when absorbance == 0 */,
+              const thz_unmix_cfg *cfg, float *d_abund /* (K, npix) */, float *d_proj /* (K, npix) or NULL */,
+              float *d_resid /* npix or NULL */, float *d_kkt /* npix or NULL */);
+int thz_host_unmix_prepare(const float *endmembers, int K, size_t L, float *G /* K x K */, float *rd /* K */);
+int thz_host_unmix_solve(const float *b, const float *G, const float *rd, int K, int n_sweeps, float *a /* K */, float *kkt);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -802,7 +858,11 @@ enum {
     THZ_BUF_CLUSTER_CENTROIDS = 29, /* (K, L) f32: the centroids the labels belong to, one mean row per cluster */
     THZ_BUF_SPARSE = 30,       /* (npix, nt_src) f32: the spike trains of the last thz_session_sparse_deconv */
     THZ_BUF_SPARSE_RESID = 31, /* (npix) f32: sum of (y - H x)^2 per trace */
-    THZ_BUF_SPARSE_NNZ = 32    /* (npix) int32: spikes per trace */
+    THZ_BUF_SPARSE_NNZ = 32,   /* (npix) int32: spikes per trace */
+    THZ_BUF_UNMIX_ABUNDANCE = 33, /* (K, npix) f32 of the last thz_session_unmix, endmember-major */
+    THZ_BUF_UNMIX_PROJ = 34,   /* (K, npix) f32: the projections b the abundances were solved from */
+    THZ_BUF_UNMIX_RESID = 35,  /* (npix) f32: sum of (u - E^T a)^2 per pixel */
+    THZ_BUF_UNMIX_KKT = 36     /* (npix) f32: the largest violation of the optimality conditions left */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -1039,6 +1099,29 @@ int thz_session_cluster(thz_session *s, int which, const thz_cluster_cfg *cfg, t
 int thz_session_cluster_step(thz_session *s, int which, const thz_cluster_cfg *cfg, const float *centroids,
                              double *sums, uint64_t *counts, double *inertia, uint64_t *changed, uint64_t *farthest);
 int thz_session_cluster_row(thz_session *s, int which, const thz_cluster_cfg *cfg, uint64_t pixel, float *row /* count */);
+
+/* thz_unmix on a resident cube.  `which` and the columns first / count / step name the matrix exactly as for
+ * thz_session_pca: THZ_BUF_AMPLITUDES, _PHASES, _DATA or _RAW, the same grids and the same THZ_ERR_NOT_READY /
+ * THZ_ERR_INVALID cases; anything else, THZ_BUF_PCA_SCORES included, is THZ_ERR_INVALID.  The spectra are read in place
+ * through the session's own pointers: the next recompute still knows their zeros.
+ * cfg->endmembers: n_endmembers x count host floats, or NULL for the resident THZ_BUF_CLUSTER_CENTROIDS — the
+ * hard-labels-to-fractions path, with no trip to the host beyond the K x L copy: THZ_ERR_NOT_READY when there are none,
+ * THZ_ERR_INVALID unless that plane holds exactly n_endmembers x count entries.  cfg->ref: count host floats when
+ * absorbance != 0.
+ * It fills the resident buffers THZ_BUF_UNMIX_ABUNDANCE (K, npix) / _PROJ (K, npix) / _RESID (npix) / _KKT (npix)
+ * (thz_session_buffer, thz_session_download; absent until the first call, and again after an upload; for the first two
+ * the pix0 / npix of thz_session_download count over the flattened array).
+ * A group has no form of its own: call this on thz_group_session_member(gs, i); every pixel is independent, so the
+ * slabs' maps are the whole grid's rows. */
+typedef struct thz_unmix_session_cfg {
+    uint32_t first, count, step;  /* the columns (bins or samples), exactly as thz_pca_cfg */
+    int32_t n_endmembers;         /* K, 1 .. THZ_UNMIX_MAX */
+    int32_t n_sweeps;             /* 0 .. THZ_UNMIX_MAX_SWEEPS */
+    int32_t absorbance;           /* as thz_unmix_cfg */
+    const float *endmembers;      /* K x count host floats; NULL: the resident k-means centroids */
+    const float *ref;             /* count host floats when absorbance != 0 */
+} thz_unmix_session_cfg;
+int thz_session_unmix(thz_session *s, int which, const thz_unmix_session_cfg *cfg);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: x-slab tiles of one cube over the GPUs of a node          */

@@ -776,6 +776,51 @@ impl GpuEngine {
         }
     }
 
+    /// Non-negative least squares of every pixel this process holds against `cfg.n_endmembers` spectra (DESIGN.md 4.12;
+    /// `thz_session_unmix` on each local member, slab after slab: every pixel is independent).  `which`:
+    /// `THZ_BUF_AMPLITUDES`, `_PHASES`, `_DATA` (whatever the walk has recorded is flushed first) or `_RAW`.
+    /// `cfg.endmembers` null takes each member's resident `THZ_BUF_CLUSTER_CENTROIDS` — the ones `cluster` left on every
+    /// member.  Every member's `THZ_BUF_UNMIX_*` stay resident.
+    /// -> (abundance (n_endmembers, gx, gy); resid, kkt (gx, gy); gx; gy)
+    pub fn unmix(&mut self, which: c_int, cfg: &ThzUnmixSessionCfg) -> Option<(Vec<f32>, Vec<f32>, Vec<f32>, usize, usize)> {
+        if self.session.is_null() || cfg.n_endmembers < 1 || cfg.n_endmembers > THZ_UNMIX_MAX { return None; }
+        if which != THZ_BUF_RAW && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy) = (0usize, 0usize);
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut rows[i as usize]);
+                    gy = self.ny;
+                } else {
+                    thz_session_grid(s, &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                }
+                if rows[i as usize] != 0 && thz_session_unmix(s, which, cfg) != THZ_OK { return None; }
+                gx += rows[i as usize];
+            }
+            let (k, npix) = (cfg.n_endmembers as usize, gx * gy);
+            let (mut abundance, mut resid, mut kkt) = (vec![0f32; k * npix], vec![0f32; npix], vec![0f32; npix]);
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                for c in 0..k { // a member's abundances are endmember-major over ITS pixels
+                    if thz_session_download(s, THZ_BUF_UNMIX_ABUNDANCE, c * mine, mine, abundance.as_mut_ptr().add(c * npix + at) as *mut c_void) != THZ_OK { return None; }
+                }
+                if thz_session_download(s, THZ_BUF_UNMIX_RESID, 0, mine, resid.as_mut_ptr().add(at) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_UNMIX_KKT, 0, mine, kkt.as_mut_ptr().add(at) as *mut c_void) != THZ_OK {
+                    return None;
+                }
+                at += mine;
+            }
+            Some((abundance, resid, kkt, gx, gy))
+        }
+    }
+
     /// the 3-D tab's instances (`update_intensity_image`, `data_thread.rs:48-101`; `gui/threed_plot.rs:132-276`) over
     /// the WHOLE grid of the group (`thz_group_session_voxels`: threshold from the whole cube, every slab's instances in
     /// x, y, z order, gathered on rank 0) — what one GPU gives for the same cube.  `InstanceData` and

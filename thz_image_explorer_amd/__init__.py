@@ -21,5 +21,7 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       ClusterCfg, ClusterOut, cluster_cfg, host_cluster_update, CLUSTER_MAX, CLUSTER_INIT_GIVEN, CLUSTER_INIT_FARTHEST,
                       BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS,
                       SparseCfg, sparse_cfg, host_sparse_trace, host_sparse_kernel, SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER,
-                      BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ)
+                      BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ,
+                      UnmixCfg, UnmixSessionCfg, unmix_session_cfg, host_unmix_prepare, host_unmix_solve, UNMIX_MAX, UNMIX_MAX_SWEEPS,
+                      BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT)
 from . import binding  # noqa: F401

@@ -120,13 +120,15 @@ BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BU
     BUF_ECHO_INDEX, BUF_ECHO_OFFSET, BUF_ECHO_VALUE, BUF_ECHO_COUNT, BUF_LAYER_THICKNESS, BUF_LAYER_DELAY, \
     BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN, \
     BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS, \
-    BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ = range(33)
+    BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ, \
+    BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT = range(37)
 SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER = 256, 4608, 4096  # THZ_SPARSE_*: taps, samples and iterations of one call
 OPTICAL_MAX_BANDS = 8
 ECHO_MAX = 4
 PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN = 512, 8, 1024  # THZ_PCA_*: columns, components, products per f32 accumulator
 CLUSTER_MAX = 16  # THZ_CLUSTER_MAX: clusters of one k-means call
 CLUSTER_INIT_GIVEN, CLUSTER_INIT_FARTHEST = range(2)  # thz_cluster_cfg's init
+UNMIX_MAX, UNMIX_MAX_SWEEPS = 16, 4096  # THZ_UNMIX_*: endmembers and sweeps of one unmixing call
 LAYER_BETWEEN, LAYER_REFERENCE = range(2)  # thz_layer_map's mode: consecutive pulses, rank 0 against a fixed arrival
 
 
@@ -225,6 +227,32 @@ class SparseCfg(C.Structure):
 
 def sparse_cfg(n_taps, center, n_iter=100, accelerate=True, step=1.0, rel_lambda=0.05, min_lambda=0.0) -> SparseCfg:
     return SparseCfg(int(n_taps), int(center), int(n_iter), int(accelerate), float(step), float(rel_lambda), float(min_lambda))
+
+
+class UnmixCfg(C.Structure):
+    """thz_unmix_cfg: endmembers, sweeps of the coordinate descent, raw values (0) or absorbance against a reference"""
+    _fields_ = [("n_endmembers", C.c_int32), ("n_sweeps", C.c_int32), ("absorbance", C.c_int32)]
+
+
+class UnmixSessionCfg(C.Structure):
+    """thz_unmix_session_cfg: the columns of the matrix, thz_unmix_cfg's three, the host endmembers (NULL: the resident
+    k-means centroids) and the host reference spectrum of the absorbance mode"""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("step", C.c_uint32), ("n_endmembers", C.c_int32),
+                ("n_sweeps", C.c_int32), ("absorbance", C.c_int32), ("endmembers", C.c_void_p), ("ref", C.c_void_p)]
+
+
+def unmix_session_cfg(first, count, step=1, n_endmembers=3, n_sweeps=256, endmembers=None, ref=None, absorbance=None) -> UnmixSessionCfg:
+    """endmembers: (n_endmembers, count) host floats, or None for the resident k-means centroids; ref: (count) host floats,
+    which turn the absorbance mode on unless `absorbance` says otherwise — the arrays are kept alive by the returned struct"""
+    on = ref is not None if absorbance is None else bool(absorbance)
+    cfg = UnmixSessionCfg(int(first), int(count), int(step), int(n_endmembers), int(n_sweeps), int(on), None, None)
+    if endmembers is not None:
+        cfg._endmembers = np.ascontiguousarray(endmembers, np.float32)
+        cfg.endmembers = cfg._endmembers.ctypes.data
+    if ref is not None:
+        cfg._ref = np.ascontiguousarray(ref, np.float32)
+        cfg.ref = cfg._ref.ctypes.data
+    return cfg
 
 
 class ThzError(RuntimeError):
@@ -366,6 +394,10 @@ SYMBOLS = [
     ("thz_host_sparse_trace", C.c_int, [_P, _SZ, _P, C.POINTER(SparseCfg), _P, _P, _P]),
     ("thz_host_sparse_kernel", C.c_int, [_P, _SZ, C.c_int, C.c_int, _P, _P]),
     ("thz_session_sparse_deconv", C.c_int, [_P, C.c_int, _P, C.POINTER(SparseCfg)]),
+    ("thz_unmix", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, C.POINTER(UnmixCfg), _P, _P, _P, _P]),
+    ("thz_host_unmix_prepare", C.c_int, [_P, C.c_int, _SZ, _P, _P]),
+    ("thz_host_unmix_solve", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    ("thz_session_unmix", C.c_int, [_P, C.c_int, C.POINTER(UnmixSessionCfg)]),
     ("thz_host_align_reference", C.c_int, [_P, _SZ, _P, _P, _SZ, _P]),
     ("thz_reference_spectrum", C.c_int, [_P, _P, _SZ, _P, _P, _SZ, C.POINTER(WindowCfg), _P, _P, _P]),
     ("thz_host_optical_properties", C.c_int, [_P, _P, _P, _P, _P, _SZ, C.c_float, _P, _P, _P]),
@@ -592,6 +624,25 @@ def host_sparse_kernel(ref, n_taps, center):
     taps, step = np.zeros(max(int(n_taps), 1), np.float32), C.c_float()
     rc = load_library().thz_host_sparse_kernel(r.ctypes.data, r.size, int(n_taps), int(center), taps.ctypes.data, C.byref(step))
     return rc, taps[:max(int(n_taps), 0)], step.value
+
+
+def host_unmix_prepare(endmembers):
+    """thz_host_unmix_prepare -> (rc, G f32 (K, K), rd f32 (K)); endmembers f32 (K, L)"""
+    e = np.ascontiguousarray(endmembers, np.float32)
+    k, width = (e.shape if e.ndim == 2 else (1, e.size))
+    g, rd = np.zeros((max(k, 1), max(k, 1)), np.float32), np.zeros(max(k, 1), np.float32)
+    rc = load_library().thz_host_unmix_prepare(e.ctypes.data, int(k), int(width), g.ctypes.data, rd.ctypes.data)
+    return rc, g, rd
+
+
+def host_unmix_solve(b, g, rd, n_sweeps):
+    """thz_host_unmix_solve of one pixel's projections b (K) -> (rc, a f32 (K), kkt)"""
+    bb = np.ascontiguousarray(b, np.float32).ravel()
+    gg, r = np.ascontiguousarray(g, np.float32), np.ascontiguousarray(rd, np.float32)
+    a, kkt = np.zeros(max(bb.size, 1), np.float32), C.c_float()
+    rc = load_library().thz_host_unmix_solve(bb.ctypes.data, gg.ctypes.data, r.ctypes.data, int(bb.size), int(n_sweeps), a.ctypes.data,
+                                             C.byref(kkt))
+    return rc, a[:bb.size], kkt.value
 
 
 def voxel_cfg_default() -> VoxelCfg:
@@ -871,6 +922,16 @@ class Session:
         self.eng._check(self.eng.lib.thz_session_cluster_row(self.h, int(which), C.byref(cfg), int(pixel), row.ctypes.data))
         return row
 
+    def unmix(self, which, cfg: "UnmixSessionCfg"):
+        """thz_session_unmix -> (abundances f32 (K, gx, gy), projections f32 (K, gx, gy), resid f32 (gx, gy), kkt f32
+        (gx, gy)); the four stay resident as THZ_BUF_UNMIX_*"""
+        self.eng._check(self.eng.lib.thz_session_unmix(self.h, int(which), C.byref(cfg)))
+        gx, gy = self._pca_pix(which)
+        k = int(cfg.n_endmembers)
+        return (self.download(BUF_UNMIX_ABUNDANCE, npix=k * gx * gy).reshape(k, gx, gy),
+                self.download(BUF_UNMIX_PROJ, npix=k * gx * gy).reshape(k, gx, gy),
+                self.download(BUF_UNMIX_RESID, npix=gx * gy).reshape(gx, gy), self.download(BUF_UNMIX_KKT, npix=gx * gy).reshape(gx, gy))
+
     def plot(self, px, py, want=None):
         """UpdateType::Plot copy-out for pixel (px, py) -> dict of host vectors"""
         nto = self.nt_out
@@ -898,6 +959,8 @@ class Session:
             out = np.empty(npix, np.float32)
         elif BUF_CLUSTER_LABELS <= which <= BUF_CLUSTER_CENTROIDS:  # npix: entries of the flattened array, likewise
             out = np.empty(npix, np.int32 if which == BUF_CLUSTER_LABELS else np.float32)
+        elif BUF_UNMIX_ABUNDANCE <= which <= BUF_UNMIX_KKT:  # npix: entries of the flattened array, likewise
+            out = np.empty(npix, np.float32)
         elif BUF_SPARSE <= which <= BUF_SPARSE_NNZ:  # pix0 / npix: pixels of the grid the spike trains were taken of
             gx, gy, nts = getattr(self, "_sparse_grid", (0, 0, 0))
             npix = max(gx * gy - pix0, 0) if npix is None else npix
@@ -1318,6 +1381,17 @@ class Engine:
         h = np.ascontiguousarray(taps, np.float32).ravel()
         self._check(self.lib.thz_sparse_deconv(self.ctx, npix, nt, _dp(data), h.ctypes.data, C.byref(cfg), _dp(out), _dp(resid),
                                                _dp(nnz)))
+
+    def unmix(self, npix, n, x, row_stride, col_step, endmembers, abund, n_sweeps=256, ref=None, absorbance=None, proj=None, resid=None,
+              kkt=None):
+        """thz_unmix on device buffers: abund and proj (K, npix), resid and kkt (npix), the last three or None; endmembers
+        (K, n) and ref (n, or None) host floats.  A reference turns the absorbance mode on unless `absorbance` says otherwise"""
+        e = np.ascontiguousarray(endmembers, np.float32)
+        r = None if ref is None else np.ascontiguousarray(ref, np.float32)
+        on = r is not None if absorbance is None else bool(absorbance)
+        cfg = UnmixCfg(e.shape[0] if e.ndim == 2 else 1, int(n_sweeps), int(on))
+        self._check(self.lib.thz_unmix(self.ctx, npix, n, _dp(x), row_stride, col_step, e.ctypes.data, None if r is None else r.ctypes.data,
+                                       C.byref(cfg), _dp(abund), _dp(proj), _dp(resid), _dp(kkt)))
 
     def arrival_plane_moments(self, nx, ny, dx, dy, dt_ps, index, offset, value, rel_threshold) -> np.ndarray:
         m = np.zeros(10, np.float64)

@@ -50,7 +50,7 @@ int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> pl
 // the call's closing synchronisation; the planes are resident when it has succeeded
 int maps_commit(thz_ctx *ctx, ResidentMaps *m);
 // A new family is a member here, its row in kMapIds (session_api.cpp) and its own *_api.cpp.
-enum MapFamily { kMapPeak, kMapOptical, kMapEcho, kMapLayer, kMapPca, kMapCluster, kMapSparse, kMapFamilies };
+enum MapFamily { kMapPeak, kMapOptical, kMapEcho, kMapLayer, kMapPca, kMapCluster, kMapSparse, kMapUnmix, kMapFamilies };
 
 struct thz_session {
     thz_ctx *ctx = nullptr;

@@ -392,6 +392,28 @@ int main(int argc, char **argv)
             CHECK(worst_m <= 1e-6, "cluster over two slabs == over one (centroids)");
             CHECK(worst_d <= 1e-4, "cluster over two slabs == over one (distances)");
             CHECK(std::fabs(o1.inertia - o2.inertia) <= 1e-5 * o1.inertia, "cluster over two slabs == over one (inertia)");
+            // the fractions behind the labels: every pixel is independent, so with the same endmembers two slabs give
+            // one slab's bits, and the resident centroids are the ones cluster() returned
+            thz_unmix_session_cfg uc{};
+            uc.first = cc.first; uc.count = cc.count; uc.step = cc.step; uc.n_endmembers = 3; uc.n_sweeps = 64;
+            uc.endmembers = m1.data();
+            std::vector<float> a1, a2, a3, r1, r2, r3, k1, k2, k3;
+            CHECK(eng.unmix(THZ_BUF_AMPLITUDES, uc, a1, r1, k1, gx1, gy1), "unmix on one slab");
+            CHECK(eng2.unmix(THZ_BUF_AMPLITUDES, uc, a2, r2, k2, gx2, gy2), "unmix on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1, "unmix: the whole grid");
+            CHECK(a1.size() == 3 * gx1 * gy1 && r1.size() == gx1 * gy1 && k1.size() == r1.size(), "unmix: sizes");
+            CHECK(a1 == a2 && r1 == r2 && k1 == k2, "unmix over two slabs == over one, bit for bit");
+            uc.endmembers = nullptr;
+            CHECK(eng.unmix(THZ_BUF_AMPLITUDES, uc, a3, r3, k3, gx1, gy1), "unmix with the resident centroids");
+            CHECK(a1 == a3 && r1 == r3 && k1 == k3, "unmix: the resident centroids are cluster()'s");
+            size_t agree = 0;
+            for (size_t p = 0; p < gx1 * gy1; ++p) {
+                int top = 0;
+                for (int k = 1; k < 3; ++k)
+                    if (a1[(size_t)k * gx1 * gy1 + p] > a1[(size_t)top * gx1 * gy1 + p]) top = k;
+                agree += top == l1[p];
+            }
+            std::printf("unmix: the largest abundance names the k-means label at %zu of %zu pixels\n", agree, gx1 * gy1);
         }
         small_bank(q.filter_by("Deconvolution"));
         q.filters_active[q.filter_chain[q.index_of("Deconvolution")]] = true;

@@ -737,6 +737,44 @@ bool GpuEngine::cluster(int which, const thz_cluster_cfg &cfg, const std::vector
     release();
     return ok;
 }
+bool GpuEngine::unmix(int which, const thz_unmix_session_cfg &cfg, std::vector<float> &abundance, std::vector<float> &resid,
+                      std::vector<float> &kkt, size_t &gx, size_t &gy)
+{
+    gx = gy = 0;
+    if (!session_ || cfg.n_endmembers < 1 || cfg.n_endmembers > THZ_UNMIX_MAX) return false;
+    if (which != THZ_BUF_RAW && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &rows[(size_t)i]);
+            gy = ny;
+        } else {
+            thz_session_grid(s, &rows[(size_t)i], &gy, nullptr, nullptr);
+        }
+        if (rows[(size_t)i] && thz_session_unmix(s, which, &cfg) != THZ_OK) return false;
+        gx += rows[(size_t)i];
+    }
+    const size_t K = (size_t)cfg.n_endmembers, npix = gx * gy;
+    abundance.assign(K * npix, 0.0f);
+    resid.assign(npix, 0.0f);
+    kkt.assign(npix, 0.0f);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = rows[(size_t)i] * gy;
+        if (!mine) continue;
+        for (size_t c = 0; c < K; ++c)  // a member's abundances are endmember-major over ITS pixels
+            if (thz_session_download(s, THZ_BUF_UNMIX_ABUNDANCE, c * mine, mine, abundance.data() + c * npix + at) != THZ_OK) return false;
+        if (thz_session_download(s, THZ_BUF_UNMIX_RESID, 0, mine, resid.data() + at) != THZ_OK
+            || thz_session_download(s, THZ_BUF_UNMIX_KKT, 0, mine, kkt.data() + at) != THZ_OK)
+            return false;
+        at += mine;
+    }
+    return true;
+}
 bool GpuEngine::download_final(std::vector<float> &cube)
 {
     if (!session_) return false;

@@ -121,6 +121,13 @@ public:
     // labels, dist2: (gx, gy); centroids: (n_clusters, count)
     bool cluster(int which, const thz_cluster_cfg &cfg, const std::vector<uint8_t> &mask, thz_cluster_out &out,
                  std::vector<int32_t> &labels, std::vector<float> &dist2, std::vector<float> &centroids, size_t &gx, size_t &gy);
+    // Non-negative least squares of every pixel this process holds against cfg.n_endmembers spectra (DESIGN.md 4.12;
+    // thz_session_unmix on each local member, slab after slab: every pixel is independent).  which: THZ_BUF_AMPLITUDES,
+    // _PHASES, _DATA (whatever the walk has recorded is flushed first) or _RAW.  cfg.endmembers NULL takes each member's
+    // resident THZ_BUF_CLUSTER_CENTROIDS — the ones cluster() left on every member.  Every member's THZ_BUF_UNMIX_* stay
+    // resident.  abundance: (n_endmembers, gx, gy); resid, kkt: (gx, gy)
+    bool unmix(int which, const thz_unmix_session_cfg &cfg, std::vector<float> &abundance, std::vector<float> &resid,
+               std::vector<float> &kkt, size_t &gx, size_t &gy);
     bool download_final(std::vector<float> &cube);                 // the whole final trace cube, rank order (tests)
 
     const thz_chain_cfg &pending() const { return pending_; }
