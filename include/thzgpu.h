@@ -751,6 +751,68 @@ int thz_unmix(thz_ctx *ctx, size_t npix, size_t L, const float *d_x, size_t row_
 int thz_host_unmix_prepare(const float *endmembers, int K, size_t L, float *G /* K x K */, float *rd /* K */);
 int thz_host_unmix_solve(const float *b, const float *G, const float *rd, int K, int n_sweeps, float *a /* K */, float *kkt);
 
+/* ------------------------------------------------------------------ */
+/* Denoising every trace: wavelet shrinkage (K23)      */
+/* ------------------------------------------------------------------ */
+/* Not a reference function.  The traces are noisy, and the Wiener multiplier (K13) amplifies whatever lies outside the
+ * reference's band; the standard remedy for THz pulses is wavelet shrinkage of the trace ("Wiener multiplier, then
+ * wavelet shrinkage" is frequency-wavelet domain deconvolution).  All device arithmetic is f32.
+ *
+ * The transform is the undecimated (stationary, a trous) wavelet transform with periodic extension: translation
+ * invariant, and defined for every trace length N = nt >= 1.  The caller passes Lf analysis taps hn[0 .. Lf) and
+ * gn[0 .. Lf) as host floats, 1 <= Lf <= THZ_WAVELET_MAX_TAPS.
+ *   forward    a_0 = y; for level j = 1 .. J and s = 2^(j-1):
+ *                  a_j[i] = chain over k = 0 .. Lf-1 ascending from +0.0f: acc = fmaf(hn[k], a_{j-1}[(i + s k) mod N], acc)
+ *                  d_j[i] = the same chain with gn
+ *              The mod is the mathematical one: s k may exceed N many times over, and N = 1 is legal.
+ *   threshold  m = the lower median of |d_1[i]|: the element of rank (N - 1) / 2 (integer division, 0-based) in
+ *              ascending order — an order statistic, whose value does not depend on how it is found.
+ *              noise_mode 0: th_j = scale[j-1] * m (one f32 product); noise_mode 1: th_j = scale[j-1].
+ *              scale: J host floats, finite and >= 0.
+ *   shrink     shrink 0 (soft): t = fabsf(d) - th; d' = t > 0 ? copysignf(t, d) : +0.0f (the sparse stage's rule).
+ *              shrink 1 (hard): d' = fabsf(d) > th ? d : +0.0f.  a_J is kept as it is.
+ *   inverse    r_J = a_J; for j = J .. 1, s = 2^(j-1):
+ *                  ch = chain over k ascending from +0.0f: fmaf(hn[k], r_j[(i - s k) mod N], acc)
+ *                  cg = chain over k ascending from +0.0f: fmaf(gn[k], d'_j[(i - s k) mod N], acc)
+ *                  r_{j-1}[i] = ch + cg   (one f32 addition)
+ *              The output is r_0.  For an orthonormal h with hn = h / sqrt 2 and gn[k] = (-1)^k hn[Lf-1-k] this
+ *              reconstructs y exactly in exact arithmetic, for every N.
+ * d_out (npix, nt) f32 is r_0; d_out == d_data (in place) is allowed, any other overlap is undefined.  d_sigma (npix) f32
+ * or NULL is m; d_kept (npix) int32 or NULL the number of d'_j[i] != 0 over all levels.
+ * Limits: 1 <= J <= THZ_WAVELET_MAX_LEVELS, nt <= THZ_WAVELET_MAX_NT and (J + 2) nt <= THZ_WAVELET_MAX_WORDS (the
+ * ping-pong pair of approximations and J detail planes of one trace in a CU's LDS: 144 KiB at J = 6, nt = 4608).
+ * Everything inside them runs.  Anything outside them, a non-finite tap or scale, a negative scale, shrink or noise_mode
+ * outside {0, 1}, nt == 0 or a NULL required pointer (all but d_sigma and d_kept) is THZ_ERR_INVALID before any launch
+ * or allocation; npix == 0 is a no-op.  A trace with a non-finite sample has unspecified values in its own outputs and
+ * affects no other row; subnormals are outside the definition; -0 and +0 compare as numbers.  d_data needs 4-byte
+ * alignment only.  The cube is read once and written once whatever J.  No floating-point atomics: the same inputs give
+ * the same bits on every run.  Time under THZ_STAGE_ECHO.
+ *
+ * thz_host_wavelet_trace is the plain-C++ twin, no GPU and no context: for finite data it equals the device bit for
+ * bit.  y and x may be the same vector.
+ * thz_host_wavelet_filter gives the Daubechies filter of order 1 .. 4 (Lf = 2, 4, 6, 8; order 1 is Haar) from the
+ * orthonormal h held as double literals in minimum-phase order: hn[k] = (float)(h[k] / sqrt 2), gn[k] =
+ * (float)((-1)^k h[Lf-1-k] / sqrt 2).  Any other order is THZ_ERR_INVALID.
+ * thz_host_wavelet_universal gives the universal threshold under the MAD noise estimate, in double:
+ * scale[j-1] = (float)((sqrt 2 / 0.6744897501960817) 2^(-j/2) sqrt(2 ln nt)) — under white noise of deviation sigma d_1
+ * has deviation sigma / sqrt 2, so sigma^ = m sqrt 2 / 0.6745, and level j's details have deviation sigma^ 2^(-j/2).
+ * THZ_ERR_INVALID for nt == 0, n_levels outside 1 .. THZ_WAVELET_MAX_LEVELS or a NULL pointer. */
+#define THZ_WAVELET_MAX_TAPS   16
+#define THZ_WAVELET_MAX_LEVELS 6
+#define THZ_WAVELET_MAX_NT     4608
+#define THZ_WAVELET_MAX_WORDS  36864  /* (J + 2) nt */
+typedef struct thz_wavelet_cfg {
+    int32_t n_taps, n_levels;    /* Lf in 1..THZ_WAVELET_MAX_TAPS, J in 1..THZ_WAVELET_MAX_LEVELS */
+    int32_t shrink, noise_mode;  /* 0 soft, 1 hard; 0: th_j = scale[j-1] * m, 1: th_j = scale[j-1] */
+} thz_wavelet_cfg;
+int thz_wavelet_denoise(thz_ctx *ctx, size_t npix, size_t nt, const float *d_data, const float *hn /* Lf host */,
+                        const float *gn /* Lf host */, const float *scale /* J host */, const thz_wavelet_cfg *cfg,
+                        float *d_out, float *d_sigma, int32_t *d_kept);
+int thz_host_wavelet_trace(const float *y, size_t nt, const float *hn, const float *gn, const float *scale,
+                           const thz_wavelet_cfg *cfg, float *x, float *sigma, int32_t *kept);
+int thz_host_wavelet_filter(int order, float *hn /* 2 order */, float *gn /* 2 order */, int *n_taps);
+int thz_host_wavelet_universal(size_t nt, int n_levels, float *scale /* n_levels */);
+
 /* Synthetic input generator for benchmarks and tests (not a reference
  * function): derivative-of-Gaussian pulse + echo + 1 % noise
  * per trace from counter-based Philox4x32-10, identical to tests/synth.py.
@@ -862,7 +924,10 @@ enum {
     THZ_BUF_UNMIX_ABUNDANCE = 33, /* (K, npix) f32 of the last thz_session_unmix, endmember-major */
     THZ_BUF_UNMIX_PROJ = 34,   /* (K, npix) f32: the projections b the abundances were solved from */
     THZ_BUF_UNMIX_RESID = 35,  /* (npix) f32: sum of (u - E^T a)^2 per pixel */
-    THZ_BUF_UNMIX_KKT = 36     /* (npix) f32: the largest violation of the optimality conditions left */
+    THZ_BUF_UNMIX_KKT = 36,    /* (npix) f32: the largest violation of the optimality conditions left */
+    THZ_BUF_DENOISED = 37,     /* (npix, nt_src) f32: the denoised traces of the last thz_session_wavelet_denoise */
+    THZ_BUF_DENOISE_SIGMA = 38, /* (npix) f32: the lower median of |d_1| per trace */
+    THZ_BUF_DENOISE_KEPT = 39  /* (npix) int32: detail coefficients kept per trace */
 };
 
 int thz_session_create(thz_ctx *ctx, size_t nx, size_t ny, size_t nt, const float *time, float dx,
@@ -1003,7 +1068,8 @@ int thz_session_echo_map(thz_session *s, int which, const thz_echo_cfg *cfg);
 int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg);
 
 /* thz_sparse_deconv on a resident cube: `which` = THZ_BUF_RAW or THZ_BUF_DATA exactly as for thz_session_peak_map (the
- * same grids, the same THZ_ERR_NOT_READY and THZ_ERR_INVALID cases).  Fills the resident buffers THZ_BUF_SPARSE
+ * same grids, the same THZ_ERR_NOT_READY and THZ_ERR_INVALID cases), or THZ_BUF_DENOISED: the denoised traces of the last
+ * thz_session_wavelet_denoise, on the grid they were taken of (THZ_ERR_NOT_READY before a denoise call).  Fills the resident buffers THZ_BUF_SPARSE
  * (npix, nt of that cube) / _SPARSE_RESID (npix f32) / _SPARSE_NNZ (npix int32) (thz_session_buffer,
  * thz_session_download with pix0 / npix in pixels; absent until the first call, and again after an upload).  The
  * session remembers the grid and time axis they belong to: thz_session_peak_map, thz_session_echo_map,
@@ -1013,6 +1079,19 @@ int thz_session_layer_map(thz_session *s, const thz_layer_cfg *cfg);
  * A group has no form of its own: call this on thz_group_session_member(gs, i); every pixel is independent, so the
  * slabs' spike trains are the whole grid's rows. */
 int thz_session_sparse_deconv(thz_session *s, int which, const float *taps, const thz_sparse_cfg *cfg);
+
+/* thz_wavelet_denoise on a resident cube: `which` = THZ_BUF_RAW or THZ_BUF_DATA exactly as for thz_session_sparse_deconv.
+ * Fills the resident buffers THZ_BUF_DENOISED (npix, nt of that cube) / _DENOISE_SIGMA (npix f32) / _DENOISE_KEPT (npix
+ * int32) (thz_session_buffer, thz_session_download with pix0 / npix in pixels; absent until the first call, and again
+ * after an upload; a refused call leaves the last result resident).  The session remembers the grid and time axis they
+ * belong to: thz_session_peak_map, thz_session_echo_map, thz_session_estimate_tilt, thz_group_session_estimate_tilt and
+ * thz_session_sparse_deconv accept `which` = THZ_BUF_DENOISED and then run on the denoised traces (THZ_ERR_NOT_READY
+ * before a denoise call).  A recompute with the Wiener multiplier followed by this call on THZ_BUF_DATA is
+ * frequency-wavelet domain deconvolution on the device.
+ * A group has no form of its own: call this on thz_group_session_member(gs, i); every pixel is independent, so the
+ * slabs' traces are the whole grid's rows. */
+int thz_session_wavelet_denoise(thz_session *s, int which, const float *hn, const float *gn, const float *scale,
+                                const thz_wavelet_cfg *cfg);
 
 /* Principal components of a resident cube.  `which` names the matrix: THZ_BUF_AMPLITUDES or THZ_BUF_PHASES (columns
  * are bins, nf = nt_out / 2 + 1 of them), THZ_BUF_DATA (samples, nt_out) — all three on the last recompute's grid, as

@@ -518,6 +518,52 @@ impl GpuEngine {
         }
     }
 
+    /// Wavelet shrinkage of every trace this process holds (`thz_session_wavelet_denoise` on each local
+    /// member, slab after slab: every pixel is independent), of the raw cube (`which = THZ_BUF_RAW`) or of the chain's
+    /// final traces (`THZ_BUF_DATA`; whatever the walk has recorded is flushed first).  `hn`, `gn`: `cfg.n_taps` analysis
+    /// taps each, e.g. `thz_host_wavelet_filter`'s; `scale`: `cfg.n_levels` thresholds, e.g.
+    /// `thz_host_wavelet_universal`'s.  Every member's `THZ_BUF_DENOISED / _DENOISE_SIGMA / _DENOISE_KEPT` stay resident.
+    /// -> (x: (gx, gy, nt_src) denoised traces; sigma, kept: (gx, gy); gx; gy; nt_src)
+    pub fn wavelet_denoise(&mut self, which: c_int, hn: &[f32], gn: &[f32], scale: &[f32], cfg: &ThzWaveletCfg) -> Option<(Vec<f32>, Vec<f32>, Vec<i32>, usize, usize, usize)> {
+        if self.session.is_null() || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) || cfg.n_taps < 1 || cfg.n_levels < 1
+            || hn.len() != cfg.n_taps as usize || gn.len() != hn.len() || scale.len() != cfg.n_levels as usize { return None; }
+        if which == THZ_BUF_DATA && !self.flush() { return None; }
+        unsafe {
+            let members = thz_group_local_count(self.group);
+            let mut rows = vec![0usize; members as usize];
+            let (mut gx, mut gy, mut nt_src) = (0usize, 0usize, 0usize);
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                if thz_session_wavelet_denoise(s, which, hn.as_ptr(), gn.as_ptr(), scale.as_ptr(), cfg) != THZ_OK { return None; }
+                if which == THZ_BUF_RAW { // the member's slab of the raw grid
+                    let mut x0 = 0usize;
+                    thz_host_slab(self.nx, thz_group_world(self.group), thz_group_rank(self.group, i), &mut x0, &mut rows[i as usize]);
+                    gy = self.ny;
+                    nt_src = self.nt;
+                } else {
+                    thz_session_grid(s, &mut rows[i as usize], &mut gy, ptr::null_mut(), ptr::null_mut());
+                    nt_src = thz_session_nt_out(s);
+                }
+                gx += rows[i as usize];
+            }
+            let npix = gx * gy;
+            let (mut x, mut sigma, mut kept) = (vec![0f32; npix * nt_src], vec![0f32; npix], vec![0i32; npix]);
+            let mut at = 0usize; // pixels of the members in front
+            for i in 0..members {
+                let s = thz_group_session_member(self.session, i);
+                let mine = rows[i as usize] * gy;
+                if mine == 0 { continue; }
+                if thz_session_download(s, THZ_BUF_DENOISED, 0, mine, x.as_mut_ptr().add(at * nt_src) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_DENOISE_SIGMA, 0, mine, sigma.as_mut_ptr().add(at) as *mut c_void) != THZ_OK
+                    || thz_session_download(s, THZ_BUF_DENOISE_KEPT, 0, mine, kept.as_mut_ptr().add(at) as *mut c_void) != THZ_OK {
+                    return None;
+                }
+                at += mine;
+            }
+            Some((x, sigma, kept, gx, gy, nt_src))
+        }
+    }
+
     /// Delays and thicknesses from the last `echo_map` (`thz_session_layer_map` on each local member): (rows, gx, gy)
     /// with rows = n_echoes - 1 between consecutive pulses (`cfg.mode` 0) and 1 against a fixed arrival (`cfg.mode` 1).
     /// A member's `THZ_BUF_LAYER_THICKNESS` stays resident: a row of it is a valid `d_thickness` of

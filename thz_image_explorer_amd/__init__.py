@@ -23,5 +23,8 @@ from .binding import (Engine, DevBuf, ThzError, load_library, LIB_PATH, SYMBOLS,
                       SparseCfg, sparse_cfg, host_sparse_trace, host_sparse_kernel, SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER,
                       BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ,
                       UnmixCfg, UnmixSessionCfg, unmix_session_cfg, host_unmix_prepare, host_unmix_solve, UNMIX_MAX, UNMIX_MAX_SWEEPS,
-                      BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT)
+                      BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT,
+                      WaveletCfg, wavelet_cfg, host_wavelet_trace, host_wavelet_filter, host_wavelet_universal,
+                      WAVELET_MAX_TAPS, WAVELET_MAX_LEVELS, WAVELET_MAX_NT, WAVELET_MAX_WORDS,
+                      BUF_DENOISED, BUF_DENOISE_SIGMA, BUF_DENOISE_KEPT)
 from . import binding  # noqa: F401

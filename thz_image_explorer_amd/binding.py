@@ -121,8 +121,11 @@ BUF_RAW, BUF_FFT, BUF_AMPLITUDES, BUF_PHASES, BUF_DATA, BUF_IMG, BUF_AVG_FFT, BU
     BUF_PCA_SCORES, BUF_PCA_COMPONENTS, BUF_PCA_MEAN, \
     BUF_CLUSTER_LABELS, BUF_CLUSTER_DIST, BUF_CLUSTER_CENTROIDS, \
     BUF_SPARSE, BUF_SPARSE_RESID, BUF_SPARSE_NNZ, \
-    BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT = range(37)
+    BUF_UNMIX_ABUNDANCE, BUF_UNMIX_PROJ, BUF_UNMIX_RESID, BUF_UNMIX_KKT, \
+    BUF_DENOISED, BUF_DENOISE_SIGMA, BUF_DENOISE_KEPT = range(40)
 SPARSE_MAX_TAPS, SPARSE_MAX_NT, SPARSE_MAX_ITER = 256, 4608, 4096  # THZ_SPARSE_*: taps, samples and iterations of one call
+# THZ_WAVELET_*: taps, levels and samples of one denoising call, and the most (levels + 2) * samples
+WAVELET_MAX_TAPS, WAVELET_MAX_LEVELS, WAVELET_MAX_NT, WAVELET_MAX_WORDS = 16, 6, 4608, 36864
 OPTICAL_MAX_BANDS = 8
 ECHO_MAX = 4
 PCA_MAX_LEN, PCA_MAX_COMPONENTS, PCA_CHAIN = 512, 8, 1024  # THZ_PCA_*: columns, components, products per f32 accumulator
@@ -227,6 +230,15 @@ class SparseCfg(C.Structure):
 
 def sparse_cfg(n_taps, center, n_iter=100, accelerate=True, step=1.0, rel_lambda=0.05, min_lambda=0.0) -> SparseCfg:
     return SparseCfg(int(n_taps), int(center), int(n_iter), int(accelerate), float(step), float(rel_lambda), float(min_lambda))
+
+
+class WaveletCfg(C.Structure):
+    """thz_wavelet_cfg: taps and levels, soft (0) or hard (1) shrinkage, thresholds times the median (0) or as given (1)"""
+    _fields_ = [("n_taps", C.c_int32), ("n_levels", C.c_int32), ("shrink", C.c_int32), ("noise_mode", C.c_int32)]
+
+
+def wavelet_cfg(n_taps, n_levels, shrink=0, noise_mode=0) -> WaveletCfg:
+    return WaveletCfg(int(n_taps), int(n_levels), int(shrink), int(noise_mode))
 
 
 class UnmixCfg(C.Structure):
@@ -394,6 +406,11 @@ SYMBOLS = [
     ("thz_host_sparse_trace", C.c_int, [_P, _SZ, _P, C.POINTER(SparseCfg), _P, _P, _P]),
     ("thz_host_sparse_kernel", C.c_int, [_P, _SZ, C.c_int, C.c_int, _P, _P]),
     ("thz_session_sparse_deconv", C.c_int, [_P, C.c_int, _P, C.POINTER(SparseCfg)]),
+    ("thz_wavelet_denoise", C.c_int, [_P, _SZ, _SZ, _P, _P, _P, _P, C.POINTER(WaveletCfg), _P, _P, _P]),
+    ("thz_host_wavelet_trace", C.c_int, [_P, _SZ, _P, _P, _P, C.POINTER(WaveletCfg), _P, _P, _P]),
+    ("thz_host_wavelet_filter", C.c_int, [C.c_int, _P, _P, C.POINTER(C.c_int)]),
+    ("thz_host_wavelet_universal", C.c_int, [_SZ, C.c_int, _P]),
+    ("thz_session_wavelet_denoise", C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(WaveletCfg)]),
     ("thz_unmix", C.c_int, [_P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, C.POINTER(UnmixCfg), _P, _P, _P, _P]),
     ("thz_host_unmix_prepare", C.c_int, [_P, C.c_int, _SZ, _P, _P]),
     ("thz_host_unmix_solve", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
@@ -626,6 +643,39 @@ def host_sparse_kernel(ref, n_taps, center):
     return rc, taps[:max(int(n_taps), 0)], step.value
 
 
+def _wavelet_vectors(hn, gn, scale):
+    """the three host vectors of a denoising call as contiguous f32; the two filters must have the same length"""
+    h, g, s = (np.ascontiguousarray(v, np.float32).ravel() for v in (hn, gn, scale))
+    if h.size != g.size:
+        raise ValueError("hn and gn differ in length")
+    return h, g, s
+
+
+def host_wavelet_trace(y, hn, gn, scale, cfg: WaveletCfg):
+    """thz_host_wavelet_trace -> (rc, x f32 (nt), sigma, kept)"""
+    a = np.ascontiguousarray(y, np.float32).ravel()
+    h, g, s = _wavelet_vectors(hn, gn, scale)
+    x = np.zeros(max(a.size, 1), np.float32)
+    sigma, kept = C.c_float(), C.c_int32()
+    rc = load_library().thz_host_wavelet_trace(a.ctypes.data, a.size, h.ctypes.data, g.ctypes.data, s.ctypes.data, C.byref(cfg),
+                                               x.ctypes.data, C.byref(sigma), C.byref(kept))
+    return rc, x[:a.size], sigma.value, kept.value
+
+
+def host_wavelet_filter(order):
+    """thz_host_wavelet_filter -> (rc, hn f32 (Lf), gn f32 (Lf)): the Daubechies analysis pair of order 1 .. 4"""
+    hn, gn, n = np.zeros(WAVELET_MAX_TAPS, np.float32), np.zeros(WAVELET_MAX_TAPS, np.float32), C.c_int(0)
+    rc = load_library().thz_host_wavelet_filter(int(order), hn.ctypes.data, gn.ctypes.data, C.byref(n))
+    return rc, hn[:n.value].copy(), gn[:n.value].copy()
+
+
+def host_wavelet_universal(nt, n_levels):
+    """thz_host_wavelet_universal -> (rc, scale f32 (n_levels)): the universal thresholds under the MAD noise estimate"""
+    scale = np.zeros(max(int(n_levels), 1), np.float32)
+    rc = load_library().thz_host_wavelet_universal(int(nt), int(n_levels), scale.ctypes.data)
+    return rc, scale[:max(int(n_levels), 0)]
+
+
 def host_unmix_prepare(endmembers):
     """thz_host_unmix_prepare -> (rc, G f32 (K, K), rd f32 (K)); endmembers f32 (K, L)"""
     e = np.ascontiguousarray(endmembers, np.float32)
@@ -833,17 +883,36 @@ class Session:
         the cube the spike trains were taken of"""
         if which == BUF_SPARSE:
             return self._sparse_grid[:2]
+        if which == BUF_DENOISED:
+            return self._denoise_grid[:2]
         return (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
 
+    def _trace_cube(self, which):
+        """(gx, gy, nt) of the cube a per-trace stage reads: THZ_BUF_RAW, THZ_BUF_DATA or the denoised traces"""
+        if which == BUF_DENOISED:
+            return self._denoise_grid
+        return (self.nx, self.ny, self.nt) if which == BUF_RAW else (*self.grid()[:2], self.nt_out)
+
     def sparse_deconv(self, which, taps, cfg: "SparseCfg"):
-        """thz_session_sparse_deconv of THZ_BUF_RAW / THZ_BUF_DATA -> (x f32 (gx, gy, nt), resid f32 (gx, gy), nnz int32
-        (gx, gy)); the spike trains stay resident as THZ_BUF_SPARSE"""
+        """thz_session_sparse_deconv of THZ_BUF_RAW / THZ_BUF_DATA / THZ_BUF_DENOISED -> (x f32 (gx, gy, nt), resid f32
+        (gx, gy), nnz int32 (gx, gy)); the spike trains stay resident as THZ_BUF_SPARSE"""
         h = np.ascontiguousarray(taps, np.float32).ravel()
         self.eng._check(self.eng.lib.thz_session_sparse_deconv(self.h, int(which), h.ctypes.data, C.byref(cfg)))
-        gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
-        self._sparse_grid = (gx, gy, self.nt if which == BUF_RAW else self.nt_out)
+        gx, gy, nts = self._trace_cube(which)
+        self._sparse_grid = (gx, gy, nts)
         return (self.download(BUF_SPARSE).reshape(gx, gy, -1), self.download(BUF_SPARSE_RESID).reshape(gx, gy),
                 self.download(BUF_SPARSE_NNZ).reshape(gx, gy))
+
+    def wavelet_denoise(self, which, hn, gn, scale, cfg: "WaveletCfg"):
+        """thz_session_wavelet_denoise of THZ_BUF_RAW / THZ_BUF_DATA -> (x f32 (gx, gy, nt), sigma f32 (gx, gy), kept int32
+        (gx, gy)); the denoised traces stay resident as THZ_BUF_DENOISED"""
+        h, g, s = _wavelet_vectors(hn, gn, scale)
+        self.eng._check(self.eng.lib.thz_session_wavelet_denoise(self.h, int(which), h.ctypes.data, g.ctypes.data, s.ctypes.data,
+                                                                 C.byref(cfg)))
+        gx, gy, nts = self._trace_cube(which)
+        self._denoise_grid = (gx, gy, nts)
+        return (self.download(BUF_DENOISED).reshape(gx, gy, -1), self.download(BUF_DENOISE_SIGMA).reshape(gx, gy),
+                self.download(BUF_DENOISE_KEPT).reshape(gx, gy))
 
     def _pca_pix(self, which):
         gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
@@ -965,6 +1034,10 @@ class Session:
             gx, gy, nts = getattr(self, "_sparse_grid", (0, 0, 0))
             npix = max(gx * gy - pix0, 0) if npix is None else npix
             out = np.empty((npix, nts) if which == BUF_SPARSE else npix, np.int32 if which == BUF_SPARSE_NNZ else np.float32)
+        elif BUF_DENOISED <= which <= BUF_DENOISE_KEPT:  # likewise the grid the denoised traces were taken of
+            gx, gy, nts = getattr(self, "_denoise_grid", (0, 0, 0))
+            npix = max(gx * gy - pix0, 0) if npix is None else npix
+            out = np.empty((npix, nts) if which == BUF_DENOISED else npix, np.int32 if which == BUF_DENOISE_KEPT else np.float32)
         elif which in per:
             gx, gy = (self.nx, self.ny) if which == BUF_RAW else self.grid()[:2]
             npix = gx * gy - pix0 if npix is None else npix
@@ -1381,6 +1454,13 @@ class Engine:
         h = np.ascontiguousarray(taps, np.float32).ravel()
         self._check(self.lib.thz_sparse_deconv(self.ctx, npix, nt, _dp(data), h.ctypes.data, C.byref(cfg), _dp(out), _dp(resid),
                                                _dp(nnz)))
+
+    def wavelet_denoise(self, npix, nt, data, hn, gn, scale, cfg: "WaveletCfg", out, sigma=None, kept=None):
+        """thz_wavelet_denoise on device buffers: out (npix, nt) f32 (may be data itself), sigma (npix) f32 and kept (npix)
+        int32 or None"""
+        h, g, s = _wavelet_vectors(hn, gn, scale)
+        self._check(self.lib.thz_wavelet_denoise(self.ctx, npix, nt, _dp(data), h.ctypes.data, g.ctypes.data, s.ctypes.data,
+                                                 C.byref(cfg), _dp(out), _dp(sigma), _dp(kept)))
 
     def unmix(self, npix, n, x, row_stride, col_step, endmembers, abund, n_sweeps=256, ref=None, absorbance=None, proj=None, resid=None,
               kkt=None):

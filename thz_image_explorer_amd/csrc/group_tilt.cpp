@@ -25,16 +25,18 @@ int thz_group_session_estimate_tilt(thz_group_session *gs, int which, int mode, 
         if (i == 0) c0 = c;
     }
     // the whole grid the slabs' maps make up, in rank order
-    // (the spike trains lie on the grid of the cube they were taken of: the raw one when the first local member's do)
+    // (the spike trains and the denoised traces lie on the grid of the cube they were taken of: the raw one when the first
+    // local member's do)
+    const bool taken = which == THZ_BUF_SPARSE || which == THZ_BUF_DENOISED;
     const bool raw_grid = which == THZ_BUF_RAW
-                          || (which == THZ_BUF_SPARSE && nl > 0 && c0.ny == gs->ny && c0.nx == gs->rows[(size_t)g->m[0].rank]);
+                          || (taken && nl > 0 && c0.ny == gs->ny && c0.nx == gs->rows[(size_t)g->m[0].rank]);
     const std::vector<size_t> &rows = raw_grid ? gs->rows : gs->cur_rows;
     const size_t ny = raw_grid ? gs->ny : gs->cur_ny;
-    for (size_t i = 0; which == THZ_BUF_SPARSE && i < nl; ++i) {
+    for (size_t i = 0; taken && i < nl; ++i) {
         SessionCube c;
         (void)session_cube(gs->sess[i], which, &c);
         if (c.nx != rows[(size_t)g->m[i].rank] || c.ny != ny)
-            return gfail(g, THZ_ERR_INVALID, "thz_group_session_estimate_tilt: the members' spike trains are not slabs of one grid");
+            return gfail(g, THZ_ERR_INVALID, "thz_group_session_estimate_tilt: the members' traces are not slabs of one grid");
     }
     size_t nx = 0;
     std::vector<size_t> counts(W);

@@ -38,12 +38,17 @@ int thz_arrival_plane_moments(thz_ctx *ctx, size_t nx, size_t ny, float dx, floa
 int session_cube(thz_session *s, int which, SessionCube *out)
 {
     thz_ctx *ctx = s->ctx;
-    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_SPARSE)
-        return fail(ctx, THZ_ERR_INVALID, "arrival times are taken of THZ_BUF_RAW, THZ_BUF_DATA or THZ_BUF_SPARSE");
+    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_SPARSE && which != THZ_BUF_DENOISED)
+        return fail(ctx, THZ_ERR_INVALID, "arrival times are taken of THZ_BUF_RAW, THZ_BUF_DATA, THZ_BUF_SPARSE or THZ_BUF_DENOISED");
     out->d = static_cast<const float *>(session_buffer_ro(s, which));
     if (which == THZ_BUF_SPARSE) {  // the spike trains, on the grid and axis of the cube they were taken of
         if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: no spike trains are resident (thz_session_sparse_deconv)");
         *out = s->sparse_cube;
+        return THZ_OK;
+    }
+    if (which == THZ_BUF_DENOISED) {  // likewise the denoised traces
+        if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: no denoised traces are resident (thz_session_wavelet_denoise)");
+        *out = s->denoised_cube;
         return THZ_OK;
     }
     if (!out->d) return fail(ctx, THZ_ERR_NOT_READY, "arrival times: the cube is not available (no recompute has run)");

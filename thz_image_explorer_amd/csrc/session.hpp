@@ -50,7 +50,7 @@ int maps_begin(thz_ctx *ctx, ResidentMaps *m, std::initializer_list<MapPlane> pl
 // the call's closing synchronisation; the planes are resident when it has succeeded
 int maps_commit(thz_ctx *ctx, ResidentMaps *m);
 // A new family is a member here, its row in kMapIds (session_api.cpp) and its own *_api.cpp.
-enum MapFamily { kMapPeak, kMapOptical, kMapEcho, kMapLayer, kMapPca, kMapCluster, kMapSparse, kMapUnmix, kMapFamilies };
+enum MapFamily { kMapPeak, kMapOptical, kMapEcho, kMapLayer, kMapPca, kMapCluster, kMapSparse, kMapUnmix, kMapDenoise, kMapFamilies };
 
 struct thz_session {
     thz_ctx *ctx = nullptr;
@@ -90,6 +90,7 @@ struct thz_session {
     // THZ_BUF_* ids, in their order (kMapIds in session_api.cpp)
     ResidentMaps maps[kMapFamilies];
     SessionCube sparse_cube;     // kMapSparse: the spike trains as a cube, on the grid, pitch and time step of the cube they were taken of
+    SessionCube denoised_cube;   // kMapDenoise: the denoised traces as a cube, likewise
     DevBuf<float> d_rawsum;      // (nt) sum over the pixels of the raw (bias-subtracted) traces, taken at upload
     DevBuf<float> d_msum;        // [Σ source trace: nt_out | Σ amplitudes: nf | Σ phases: nf] of the last recompute, undivided
     bool msum_fast = false;      // the last recompute left its undivided sums in d_msum (want_means == 1)
@@ -198,8 +199,8 @@ int session_means(thz_session *s, const thz_chain_cfg *cfg, size_t total_pix);
 int session_roi_sums(thz_session *s, const thz_chain_cfg *cfg, bool *data_only);
 int session_roi_finish(thz_session *s, const thz_chain_cfg *cfg, bool data_only);
 size_t session_roi_floats(const thz_session *s);
-// peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA, or THZ_BUF_SPARSE: the spike trains, on the grid
-// and time axis of the cube they were taken of) with its grid, trace length and the mean step of its time axis;
+// peak_api.cpp: the cube `which` names (THZ_BUF_RAW / THZ_BUF_DATA, or THZ_BUF_SPARSE / THZ_BUF_DENOISED: the spike trains
+// or the denoised traces, on the grid and time axis of the cube they were taken of) with its grid, trace length and the mean step of its time axis;
 // THZ_ERR_NOT_READY when it is absent
 int session_cube(thz_session *s, int which, SessionCube *out);
 // the ifft stage's avg_data (avg_in_fourier_space; needs the means): host-side, after session_means

@@ -721,10 +721,12 @@ namespace {
 // A family's ids are contiguous and in the order of its planes: the first id and how many.  The arrival-time, echo and
 // spike-train maps belong to whichever cube was mapped last, the raw one included; the optical-property maps to the
 // spectra of the recompute they were taken of; the layer maps to the echo maps they were made of; the principal
-// components, the segmentation and the abundances to whichever matrix they were taken of.
+// components, the segmentation and the abundances to whichever matrix they were taken of; the denoised traces to
+// whichever cube they were taken of.
 const struct { int first, planes; } kMapIds[kMapFamilies] = {
     {THZ_BUF_PEAK_INDEX, 3}, {THZ_BUF_OPT_N, 5},          {THZ_BUF_ECHO_INDEX, 4}, {THZ_BUF_LAYER_THICKNESS, 2},
-    {THZ_BUF_PCA_SCORES, 3}, {THZ_BUF_CLUSTER_LABELS, 3}, {THZ_BUF_SPARSE, 3},     {THZ_BUF_UNMIX_ABUNDANCE, 4}};
+    {THZ_BUF_PCA_SCORES, 3}, {THZ_BUF_CLUSTER_LABELS, 3}, {THZ_BUF_SPARSE, 3},     {THZ_BUF_UNMIX_ABUNDANCE, 4},
+    {THZ_BUF_DENOISED, 3}};
 
 // the plane `which` names (and its family), resident or not; null: `which` is no analysis map
 const MapPlane *map_plane(const thz_session *s, int which, const ResidentMaps **family = nullptr)

@@ -37,8 +37,8 @@ int thz_session_sparse_deconv(thz_session *s, int which, const float *taps, cons
     thz_ctx *ctx = s->ctx;
     if (int rc = use_device(ctx)) return rc;
     if (!taps || !cfg) return fail(ctx, THZ_ERR_INVALID, "thz_session_sparse_deconv: a required pointer is NULL");
-    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA)
-        return fail(ctx, THZ_ERR_INVALID, "thz_session_sparse_deconv: the traces are THZ_BUF_RAW or THZ_BUF_DATA");
+    if (which != THZ_BUF_RAW && which != THZ_BUF_DATA && which != THZ_BUF_DENOISED)
+        return fail(ctx, THZ_ERR_INVALID, "thz_session_sparse_deconv: the traces are THZ_BUF_RAW, THZ_BUF_DATA or THZ_BUF_DENOISED");
     SessionCube c;
     if (int rc = session_cube(s, which, &c)) return rc;
     if (const char *why = sparse_cfg_error(cfg, c.nt, taps)) return fail(ctx, THZ_ERR_INVALID, std::string("thz_session_sparse_deconv: ") + why);

@@ -336,6 +336,39 @@ int main(int argc, char **argv)
             CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && i1 == i2 && c1 == c2, "echo_map of the spike trains over two slabs == over one");
         }
         {
+            // wavelet shrinkage of the raw cube, on one slab and on two: every pixel is independent and every sum has one
+            // order, so the slabs' denoised traces are the whole grid's rows bit for bit
+            thz_wavelet_cfg wc{};
+            wc.n_levels = 4; wc.shrink = 1; wc.noise_mode = 0;
+            std::vector<float> hn(8), gn(8), scale(4);
+            int n_taps = 0;
+            CHECK(thz_host_wavelet_filter(4, hn.data(), gn.data(), &n_taps) == THZ_OK && n_taps == 8, "wavelet filter");
+            wc.n_taps = n_taps;
+            CHECK(thz_host_wavelet_universal((size_t)c.nt, wc.n_levels, scale.data()) == THZ_OK, "universal thresholds");
+            std::vector<float> x1, x2, s1, s2;
+            std::vector<int32_t> k1, k2;
+            size_t gx1 = 0, gy1 = 0, gx2 = 0, gy2 = 0, nt1 = 0, nt2 = 0;
+            CHECK(eng.wavelet_denoise(THZ_BUF_RAW, hn, gn, scale, wc, x1, s1, k1, gx1, gy1, nt1), "wavelet_denoise on one slab");
+            CHECK(eng2.wavelet_denoise(THZ_BUF_RAW, hn, gn, scale, wc, x2, s2, k2, gx2, gy2, nt2), "wavelet_denoise on two slabs");
+            CHECK(gx1 == (size_t)c.nx && gy1 == (size_t)c.ny && gx2 == gx1 && gy2 == gy1 && nt1 == (size_t)c.nt && nt2 == nt1, "wavelet_denoise: the whole grid");
+            CHECK(x1.size() == gx1 * gy1 * nt1 && s1.size() == gx1 * gy1 && k1.size() == s1.size(), "wavelet_denoise: sizes");
+            CHECK(x1.size() == x2.size() && std::memcmp(x1.data(), x2.data(), x1.size() * sizeof(float)) == 0 && k1 == k2
+                      && std::memcmp(s1.data(), s2.data(), s1.size() * sizeof(float)) == 0,
+                  "wavelet_denoise over two slabs == over one");
+            // the device against the host function on one trace
+            std::vector<float> hx(nt1), y5(nt1);
+            float hs = 0.0f;
+            int32_t hk = 0;
+            for (size_t i = 0; i < nt1; ++i) y5[i] = c.raw[5 * nt1 + i] - c.raw[5 * nt1];  // as uploaded: the first sample taken off
+            CHECK(thz_host_wavelet_trace(y5.data(), nt1, hn.data(), gn.data(), scale.data(), &wc, hx.data(), &hs, &hk) == THZ_OK, "host wavelet trace");
+            bool same = hk == k1[5] && hs == s1[5];
+            for (size_t i = 0; i < nt1; ++i) same = same && hx[i] == x1[5 * nt1 + i];
+            CHECK(same, "wavelet_denoise == thz_host_wavelet_trace on a trace");
+            size_t kept = 0;
+            for (int32_t n : k1) kept += (size_t)n;
+            std::printf("wavelet_denoise: %.1f coefficients kept per trace of %zu samples\n", (double)kept / (double)k1.size(), nt1);
+        }
+        {
             // principal components of the resident amplitudes, on one slab and on two: the slabs' sums and Gram matrices
             // are added in f64, so the eigenvalues agree far inside the Gram matrix's own f32 error, and the scores to
             // the f32 rounding of the components

@@ -486,6 +486,48 @@ bool GpuEngine::sparse_deconv(int which, const std::vector<float> &taps, const t
     sparse_gy_ = gy;
     return true;
 }
+bool GpuEngine::wavelet_denoise(int which, const std::vector<float> &hn, const std::vector<float> &gn, const std::vector<float> &scale,
+                                const thz_wavelet_cfg &cfg, std::vector<float> &x, std::vector<float> &sigma,
+                                std::vector<int32_t> &kept, size_t &gx, size_t &gy, size_t &nt_src)
+{
+    gx = gy = nt_src = 0;
+    if (!session_ || (which != THZ_BUF_RAW && which != THZ_BUF_DATA) || cfg.n_taps < 1 || cfg.n_levels < 1
+        || hn.size() != (size_t)cfg.n_taps || gn.size() != hn.size() || scale.size() != (size_t)cfg.n_levels)
+        return false;
+    if (which == THZ_BUF_DATA && !flush()) return false;
+    const int members = thz_group_local_count(group_);
+    std::vector<size_t> rows((size_t)members, 0);
+    for (int i = 0; i < members; ++i) {  // slab after slab: every pixel is independent
+        thz_session *s = thz_group_session_member(session_, i);
+        if (thz_session_wavelet_denoise(s, which, hn.data(), gn.data(), scale.data(), &cfg) != THZ_OK) return false;
+        if (which == THZ_BUF_RAW) {  // the member's slab of the raw grid
+            size_t x0 = 0;
+            thz_host_slab(nx, thz_group_world(group_), thz_group_rank(group_, i), &x0, &rows[(size_t)i]);
+            gy = ny;
+            nt_src = nt;
+        } else {
+            thz_session_grid(s, &rows[(size_t)i], &gy, nullptr, nullptr);
+            nt_src = thz_session_nt_out(s);
+        }
+        gx += rows[(size_t)i];
+    }
+    const size_t npix = gx * gy;
+    x.assign(npix * nt_src, 0.0f);
+    sigma.assign(npix, 0.0f);
+    kept.assign(npix, 0);
+    size_t at = 0;  // pixels of the members in front
+    for (int i = 0; i < members; ++i) {
+        thz_session *s = thz_group_session_member(session_, i);
+        const size_t mine = rows[(size_t)i] * gy;
+        if (!mine) continue;
+        if (thz_session_download(s, THZ_BUF_DENOISED, 0, mine, x.data() + at * nt_src) != THZ_OK
+            || thz_session_download(s, THZ_BUF_DENOISE_SIGMA, 0, mine, sigma.data() + at) != THZ_OK
+            || thz_session_download(s, THZ_BUF_DENOISE_KEPT, 0, mine, kept.data() + at) != THZ_OK)
+            return false;
+        at += mine;
+    }
+    return true;
+}
 bool GpuEngine::layer_map(const thz_layer_cfg &cfg, std::vector<float> &thickness, std::vector<float> &delay, size_t &rows,
                           size_t &gx, size_t &gy)
 {

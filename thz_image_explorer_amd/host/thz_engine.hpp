@@ -100,6 +100,15 @@ public:
     // x: (gx, gy, nt_src) spike trains; resid, nnz: (gx, gy)
     bool sparse_deconv(int which, const std::vector<float> &taps, const thz_sparse_cfg &cfg, std::vector<float> &x,
                        std::vector<float> &resid, std::vector<int32_t> &nnz, size_t &gx, size_t &gy, size_t &nt_src);
+    // Wavelet shrinkage of every trace this process holds (thz_session_wavelet_denoise on each local
+    // member, slab after slab: every pixel is independent), of the raw cube (which = THZ_BUF_RAW) or of the chain's final
+    // traces (THZ_BUF_DATA; whatever the walk has recorded is flushed first).  hn, gn: cfg.n_taps analysis taps each, e.g.
+    // thz_host_wavelet_filter's; scale: cfg.n_levels thresholds, e.g. thz_host_wavelet_universal's.  Every member's
+    // THZ_BUF_DENOISED / _DENOISE_SIGMA / _DENOISE_KEPT stay resident.
+    // x: (gx, gy, nt_src) denoised traces; sigma, kept: (gx, gy)
+    bool wavelet_denoise(int which, const std::vector<float> &hn, const std::vector<float> &gn, const std::vector<float> &scale,
+                         const thz_wavelet_cfg &cfg, std::vector<float> &x, std::vector<float> &sigma, std::vector<int32_t> &kept,
+                         size_t &gx, size_t &gy, size_t &nt_src);
     // Principal components of everything this process holds: the covariance is not pixel-independent, so
     // thz_session_pca_sums and thz_session_pca_gram run on each local member, the members' sums and Gram matrices are
     // added here in member order (f64), thz_host_pca_components runs once, and thz_session_pca_project fills each
